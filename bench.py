@@ -200,6 +200,8 @@ def main():
     ap.add_argument("--chain-variants", action="store_true", help="--full-chain block on more than one rank: also time the chunked and the "
                     "chunked + overlapped forms (on one rank they are always timed); off by default there -- the overlapped form issues its collectives "
                     "from a worker thread, which no multi-GPU box has run yet, and a secondary figure must not be able to take the N-rank line down")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes what the last timed step computed to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all): packed detections and their counts, the per-frame detection rows, fitted rows")
     ap.add_argument("--dump-chain", default="", help="every rank r writes tracks, fits and merge result of the --full-chain block to <path>.r<r>.npz")
     ap.add_argument("--only-chain", action="store_true", help="run nothing but the --full-chain block (tests)")
     ap.add_argument("--no-pin", action="store_true", help="leave odam_config cg.pin at 0 (kernel choice by problem size: a rank's result then "
@@ -365,6 +367,13 @@ def main():
                                      det_phase_ms / args.steps, last)
     if args.dump and rank == 0:
         np.savez(args.dump, blk=dump["blk"], cnt=dump["cnt"], fitted=dump["fitted"])
+    if args.dump_outputs and rank == 0:
+        rows = [np.asarray(r, np.float64).reshape(-1, 79) for r in dump["per_frame"]]
+        dump_outputs(args.dump_outputs, {
+            "detections": dump["blk"],                                            # float32 [frames, 30, 15], -1 past the count
+            "detection_counts": dump["cnt"].astype(np.float32),                   # [frames]
+            "detection_rows": np.concatenate(rows) if rows else np.zeros((0, 79)),  # float64 [detections, 79], this rank's frames in order
+            "fitted": dump["fitted"]})                                            # float32 [objects, 33]: 9 SQ parameters + 8 box corners
     if ws > 1:
         t = torch.tensor([dt], device=device if args.backend == "nccl" else "cpu", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -541,6 +550,21 @@ def main():
         result["cpu_baseline"] = cpu_baseline(scene, tracks, N)
     if rank == 0:
         print(json.dumps(result))
+
+
+def dump_outputs(path, arrays, limit=64 << 20):
+    """arrays {name: ndarray} -> path/<name>.npy in float32 / float64.  Past `limit` bytes in all, each array is cut to a seeded sample of
+    its rows, the same fraction for all (indices in path/<name>_sample_index.npy), so two runs with the same arguments still write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a) if np.asarray(a).dtype in (np.float32, np.float64) else np.asarray(a, np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.ndim and len(a) > 1:
+            keep = max(1, int(len(a) * 0.95 * limit / total))
+            idx = np.sort(np.random.RandomState(0).choice(len(a), keep, replace=False))
+            a = a[idx]
+            np.save(os.path.join(path, f"{name}_sample_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def secondary_blocks(step, detector, chunk, frames, tracks, N, per_frame, scene, device, ms_step_s, det_phase_ms_step, last):

@@ -56,14 +56,6 @@ def test_host_sampler_matches_reference_golden(golden):
         assert np.array_equal(ho.view(np.uint32), om.view(np.uint32))
 
 
-def _ref_sampler():
-    import pytest
-    so = os.path.join(REPO, "oracle", "_ref", "libodam_ref_sampler.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (needs /root/reference: make -C oracle ref)")
-    return ctypes.CDLL(so)
-
-
 def _call_sample_on_batch(L, shapes, eps, N, buffer_size, seed):
     fp = ctypes.POINTER(ctypes.c_float)
     B, M = shapes.shape[:2]
@@ -75,22 +67,20 @@ def _call_sample_on_batch(L, shapes, eps, N, buffer_size, seed):
     return et, om
 
 
-def test_sample_on_batch_has_the_reference_signature_and_bits():
+def test_sample_on_batch_has_the_reference_signature_and_bits(golden):
     """`sample_on_batch(float*, float*, float*, float*, int B, int M, int N, int buffer_size, int seed)` exported by
     libodam_amd.so (what _sampler.pyx:430-439 binds) against the reference's own sampling.cpp compiled as it lies
-    (oracle/_ref): B, M > 1, N != 1000, other buffer sizes and seeds -- bit for bit."""
+    (tests/golden/ref_sampler.npz, make_golden_ref_sampler.py): B, M > 1, N != 1000, other buffer sizes and seeds -- bit for bit."""
     from odam_amd import _lib
-    ref = _ref_sampler()
     L = _lib.lib()
-    rs = np.random.RandomState(5)
-    for B, M, N, nbuf, seed in ((1, 1, 1000, 201, 0), (2, 3, 257, 201, 0), (3, 2, 1000, 101, 7), (1, 5, 64, 513, 123456),
-                                (4, 1, 1, 2, 1), (1, 2, 2048, 3, 99), (2, 2, 100, 1001, 2 ** 31 - 1)):
-        shapes = rs.uniform(0.02, 1.6, (B, M, 3)).astype(np.float32)
-        eps = rs.uniform(0.2, 1.6, (B, M, 2)).astype(np.float32)
+    z = golden("ref_sampler.npz")
+    assert len(z["abi_cases"]) == 7
+    for k, (B, M, N, nbuf, seed) in enumerate(z["abi_cases"].tolist()):
+        shapes, eps = z[f"abi_c{k}_shapes"], z[f"abi_c{k}_eps"]
+        assert shapes.shape == (B, M, 3) and eps.shape == (B, M, 2)
         ge, go = _call_sample_on_batch(L, shapes.copy(), eps.copy(), N, nbuf, seed)
-        re_, ro = _call_sample_on_batch(ref, shapes.copy(), eps.copy(), N, nbuf, seed)
-        assert np.array_equal(ge.view(np.uint32), re_.view(np.uint32)), (B, M, N, nbuf, seed)
-        assert np.array_equal(go.view(np.uint32), ro.view(np.uint32)), (B, M, N, nbuf, seed)
+        assert np.array_equal(ge.view(np.uint32), z[f"abi_c{k}_etas"].view(np.uint32)), (B, M, N, nbuf, seed)
+        assert np.array_equal(go.view(np.uint32), z[f"abi_c{k}_omegas"].view(np.uint32)), (B, M, N, nbuf, seed)
 
 
 def test_sample_on_batch_agrees_with_the_pipeline_call(golden):

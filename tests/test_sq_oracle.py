@@ -1,6 +1,5 @@
 """The CPU oracle (oracle/sq_oracle.c) against vectors produced by the reference itself
 (tests/golden/make_golden.py imported likojack/ODAM in the build container)."""
-import ctypes
 import os
 
 import numpy as np
@@ -26,22 +25,16 @@ def test_sampler_bit_exact_vs_reference_binding(oracle, golden):
         assert np.array_equal(oo.view(np.uint32), om.view(np.uint32))
 
 
-def test_sampler_bit_exact_vs_reference_cpp_build(oracle):
-    """oracle/_ref/libodam_ref_sampler.so is the reference's own sampling.cpp compiled by oracle/Makefile."""
-    so = os.path.join(REPO, "oracle", "_ref", "libodam_ref_sampler.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (reference sources absent on this box)")
-    R = ctypes.CDLL(so)
-    rs = np.random.RandomState(5)
-    fp = oracle.fp
-    for _ in range(300):
-        a = rs.uniform(0.02, 1.6, 3).astype(np.float32); e = rs.uniform(0.2, 1.6, 2).astype(np.float32)
-        et = np.zeros(1000, np.float32); om = np.zeros(1000, np.float32)
-        R.sample_on_batch(a.ctypes.data_as(fp), e.ctypes.data_as(fp), et.ctypes.data_as(fp),
-                          om.ctypes.data_as(fp), 1, 1, 1000, 201, 0)
+def test_sampler_bit_exact_vs_reference_cpp_build(oracle, golden):
+    """against the reference's own sampling.cpp compiled by oracle/Makefile: 300 (a, e) pairs, the sha256 of its
+    etas || omegas stored in tests/golden/ref_sampler.npz (make_golden_ref_sampler.py)."""
+    import hashlib
+    z = golden("ref_sampler.npz")
+    assert len(z["pipe_a"]) == 300
+    for k, (a, e) in enumerate(zip(z["pipe_a"], z["pipe_e"])):
         oe, oo = oracle.sample(a, e)
-        assert np.array_equal(oe.view(np.uint32), et.view(np.uint32))
-        assert np.array_equal(oo.view(np.uint32), om.view(np.uint32))
+        d = hashlib.sha256(oe.tobytes() + oo.tobytes()).digest()
+        assert d == z["pipe_sha256"][k].tobytes(), (k, a, e)
 
 
 def _cases(z):
