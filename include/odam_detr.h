@@ -158,6 +158,16 @@ int odam_op_attention_bf16(const void* Q, int ldq, const void* K, int ldk, const
                            int B, int H, int Lq, int Lk, void* stream);
 int odam_op_add_layernorm(const float* x, const float* r, const float* gamma, const float* beta, float* y, int M,
                           void* stream);
+/* Attention as the networks call it, for parity tests.  head_dim 32: dtype 0 fp32 / 1 bf16 (row pitches multiples of 4 / 8
+ * elements, ldo of 4), key_mask [dev][B][Lk] nullable (non-zero = padded key), the detector's kernel choice (att.x3 /
+ * att.bf16_mfma apply).  head_dim 64: dtype 0 and key_mask null only (the associator's kernel, scale 1/8).  Code 1 for any
+ * other head_dim / dtype / mask combination. */
+int odam_op_attention_ex(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                         int B, int H, int Lq, int Lk, int head_dim, int dtype, const unsigned char* key_mask, void* stream);
+/* residual add + LayerNorm over 256 channels as the forward calls it: x, r (nullable), y, y_pos (nullable) [dev][M][256] of
+ * dtype 0 fp32 / 1 bf16, gamma / beta / pos fp32; y = LN(x + r) * gamma + beta, y_pos[row] = y[row] + pos[row % L] */
+int odam_op_add_layernorm_ex(const void* x, const void* r, const float* gamma, const float* beta, void* y,
+                             const float* pos, int L, void* y_pos, int M, int dtype, void* stream);
 int odam_op_maxpool3x3s2_nhwc(const float* x, float* y, int B, int H, int W, int C, void* stream);
 
 #ifdef __cplusplus

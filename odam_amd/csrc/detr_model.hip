@@ -861,10 +861,37 @@ extern "C" int odam_op_attention_bf16(const void* Q, int ldq, const void* K, int
     return odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, 1, (hipStream_t)stream);
 }
 
+extern "C" int odam_op_attention_ex(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                                    int B, int H, int Lq, int Lk, int head_dim, int dtype, const unsigned char* key_mask,
+                                    void* stream) {
+    if (!Q || !K || !V || !O) return odam_fail(1, "odam_op_attention_ex: null pointer");
+    if (B < 0 || H < 0 || Lq < 0 || Lk < 0) return odam_fail(1, "odam_op_attention_ex: negative extent");
+    if (dtype != 0 && dtype != 1) return odam_fail(1, "odam_op_attention_ex: dtype must be 0 (fp32) or 1 (bf16)");
+    const int pm = dtype == 1 ? 8 : 4;      // 16-byte rows of Q / K / V (the bf16 kernel's uint4 loads); O in 4-element groups
+    if (ldq % pm || ldk % pm || ldv % pm || ldo % 4)
+        return odam_fail(1, "odam_op_attention_ex: row pitches must be multiples of 8 / 8 / 8 / 4 (bf16) or 4 (fp32) elements");
+    if (H == 0) return 0;
+    if (head_dim == 32)
+        return odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, dtype, (hipStream_t)stream, key_mask);
+    if (head_dim == 64 && dtype == 0 && !key_mask)
+        return odam_dk::launch_attention_d64((const float*)Q, ldq, (const float*)K, ldk, (const float*)V, ldv, (float*)O, ldo,
+                                             B, H, Lq, Lk, (hipStream_t)stream);
+    return odam_fail(1, "odam_op_attention_ex: head_dim 32 (fp32 / bf16, optional key mask) or 64 (fp32, no mask) only");
+}
+
 extern "C" int odam_op_add_layernorm(const float* x, const float* r, const float* gamma, const float* beta, float* y,
                                      int M, void* stream) {
     if (!x || !gamma || !beta || !y) return odam_fail(1, "odam_op_add_layernorm: null pointer");
     return odam_dk::launch_add_layernorm(x, r, gamma, beta, y, nullptr, 1, nullptr, M, 0, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_add_layernorm_ex(const void* x, const void* r, const float* gamma, const float* beta, void* y,
+                                        const float* pos, int L, void* y_pos, int M, int dtype, void* stream) {
+    if (!x || !gamma || !beta || !y) return odam_fail(1, "odam_op_add_layernorm_ex: null pointer");
+    if (y_pos && (!pos || L <= 0)) return odam_fail(1, "odam_op_add_layernorm_ex: y_pos needs pos and L > 0");
+    if (dtype != 0 && dtype != 1) return odam_fail(1, "odam_op_add_layernorm_ex: dtype must be 0 (fp32) or 1 (bf16)");
+    if (M < 0) return odam_fail(1, "odam_op_add_layernorm_ex: negative M");
+    return odam_dk::launch_add_layernorm(x, r, gamma, beta, y, pos, y_pos ? L : 1, y_pos, M, dtype, (hipStream_t)stream);
 }
 
 extern "C" int odam_op_maxpool3x3s2_nhwc(const float* x, float* y, int B, int H, int W, int C, void* stream) {

@@ -23,6 +23,26 @@ def sd():
     return weights.make_state_dict(seed=0)
 
 
+def test_bf16_attention_key_mask():
+    """_attention_b with a key-padding mask: masked keys have no influence on the output bits, and the result is the float64
+    masked softmax up to the bf16 roundings the oracle models (P and O, 2^-8 each); the fma form of the exponent agrees too"""
+    g = torch.Generator().manual_seed(0)
+    q = O._rb(torch.randn(2, 70, 256, generator=g))
+    k, v = O._rb(torch.randn(2, 150, 256, generator=g)), O._rb(torch.randn(2, 150, 256, generator=g))
+    mask = torch.zeros(2, 150, dtype=torch.bool)
+    mask[0, :64] = True               # the whole first tile
+    mask[1, 100:] = True              # the tail tile and part of the second
+    s = (q.double().reshape(2, 70, 8, 32).transpose(1, 2) @ k.double().reshape(2, 150, 8, 32).permute(0, 2, 3, 1)) * (1 / 32) ** 0.5
+    p = torch.softmax(s.masked_fill(mask[:, None, None, :], -float("inf")), -1)
+    ref = (p @ v.double().reshape(2, 150, 8, 32).transpose(1, 2)).transpose(1, 2).reshape(2, 70, 256)
+    k2, v2 = k.clone(), v.clone()
+    k2[mask], v2[mask] = 64.0, -1000.0
+    for fma in (False, True):
+        got = O._attention_b(q, k, v, 8, key_mask=mask, fma=fma)
+        assert torch.equal(got, O._attention_b(q, k2, v2, 8, key_mask=mask, fma=fma))
+        assert ((got.double() - ref).abs() <= 2.0 ** -8 * (v.abs().max() + ref.abs()) + 1e-6).all()
+
+
 def test_full_size_forward_matches_reference_detr(sd, golden):
     """oracle vs the reference's DETR on one 3x800x1066 frame"""
     z = golden("detr_full.npz")
