@@ -24,7 +24,8 @@ extern "C" {
 typedef struct odam_detr odam_detr;
 
 typedef struct {
-    int resnet_blocks[4];  /* {3,4,6,3} = resnet50, {3,4,23,3} = resnet101 (backbone.py:90) */
+    int resnet_blocks[4];  /* blocks per stage (backbone.py:90): Bottleneck {3,4,6,3} = resnet50, {3,4,23,3} = resnet101,
+                              {3,8,36,3} = resnet152; BasicBlock (basic_block = 1) {2,2,2,2} = resnet18, {3,4,6,3} = resnet34 */
     int hidden_dim;        /* 256  (configs/detr_scan_net.yaml) */
     int nheads;            /* 8    head dim must be 32 */
     int dim_feedforward;   /* 2048 */
@@ -42,6 +43,9 @@ typedef struct {
                               LayerNorm "transformer.encoder.norm.*" (src/models/transformer.py:169-188, 240-262, 26-28) */
     int dilation;          /* 1: the DC5 backbone (src/models/backbone.py:89-91): layer4 keeps layer3's resolution -- stride 1, its
                               3x3 filters dilated by 2 from the second block on -- so the token grid is ceil(H/16) x ceil(W/16) */
+    int basic_block;       /* 0: torchvision Bottleneck (1x1 reduce, 3x3, 1x1 expand; layer4 has 2048 channels).  1: torchvision
+                              BasicBlock (resnet18 / resnet34: 3x3 with the stage's stride, 3x3 + identity or 1x1 downsample; layer4
+                              has 512 channels).  BasicBlock with `dilation` is refused, as torchvision refuses it */
 } odam_detr_cfg;
 
 int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out);
@@ -85,7 +89,7 @@ int odam_detr_forward_masked(odam_detr* m, const float* img, int B, const unsign
                              float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
                              float* obj_features, void* stream);
 
-/* optional taps for parity tests: layer4 feature map as NCHW [B,2048,h,w] and encoder memory [B,h*w,hidden]
+/* optional taps for parity tests: layer4 feature map as NCHW [B,C4,h,w] (C4 = 2048 Bottleneck, 512 BasicBlock) and encoder memory [B,h*w,hidden]
  * of the most recent forward (either may be null) */
 int odam_detr_debug_read(odam_detr* m, int B, float* layer4_nchw, float* memory, void* stream);
 

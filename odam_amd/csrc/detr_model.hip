@@ -40,8 +40,8 @@ struct Conv {          // packed convolution / linear layer on device
     int k_order = 0;         // conv_gemm.h: 1 = channel-chunk-major K (multi-tap filters with Cin % k-tile == 0)
 };
 
-struct Bottleneck {
-    Conv c1, c2, c3, ds;
+struct Bottleneck {     // one residual block: Bottleneck c1 1x1, c2 3x3 (stride), c3 1x1 + residual; BasicBlock (odam_detr::basic)
+    Conv c1, c2, c3, ds;   //   c1 3x3 (stride), c2 3x3 + residual, c3 unused
     bool has_ds = false;
 };
 
@@ -62,6 +62,8 @@ struct odam_detr {
     std::vector<void*> allocs;
 
     Conv stem;
+    bool basic = false;          // cfg.basic_block: the blocks are torchvision BasicBlocks
+    int l4_ch = 2048;            // channels of the layer4 map (512 for BasicBlock bodies), from the packed weights
     std::vector<Bottleneck> blocks;
     std::vector<int> block_stride;
     Conv input_proj;
@@ -220,6 +222,15 @@ int pack_ln(odam_detr* m, LN& ln, const std::string& prefix) {
     return m->upload(&ln.b, b->data);
 }
 
+// a filter of the BasicBlock plan has the shape that plan reads ([Cout, Cin, k, k]): a Bottleneck checkpoint under a BasicBlock
+// configuration fails here, by name, instead of being read out of bounds
+int check_shape(const HostTensor& w, int cout, int cin, int k, const std::string& name) {
+    if (w.shape.size() == 4 && w.shape[0] == cout && w.shape[1] == cin && w.shape[2] == k && w.shape[3] == k) return 0;
+    std::snprintf(g_odam_err, sizeof(g_odam_err), "odam_detr_finalize: %s must be [%d, %d, %d, %d] for this backbone", name.c_str(),
+                  cout, cin, k, k);
+    return 1;
+}
+
 int run_conv(const Conv& c, const void* x, int B, int H, int W, const void* res, bool relu, void* y, int ldc,
              hipStream_t st, int dtype = 0, int out_f32 = 0) {
     ConvGemmArgs a{};
@@ -261,6 +272,7 @@ int conv_t(odam_detr* m, const Conv& c, const void* x, int B, int H, int W, cons
 int fused_c2c3_t(odam_detr* m, const Conv& c2, const Conv& c3, const void* x, int B, int H, int W, const void* res, void* y,
                  hipStream_t st, const Conv* next_c1 = nullptr, void* t_next = nullptr, bool* chained = nullptr) {
     if (chained) *chained = false;
+    if (m->basic) return -1;         // BasicBlock bodies have no expand layer: nothing of this applies
     if (c2.dil != 1) return -1;      // dilated 3x3 (the DC5 backbone's layer4): the separate launches
     if (c3.KH != 1 || c3.stride != 1 || c3.Kpad != c2.Cout) return -1;
     if (!m->dt && (!c2.w3 || !c3.w3)) return -1;
@@ -392,8 +404,14 @@ extern "C" int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out) {
         return odam_fail(3, "odam_detr_create: kernels are built for hidden_dim 256, 8 heads (head dim 32)");
     if (cfg->max_batch < 1 || cfg->img_h < 32 || cfg->img_w < 32) return odam_fail(1, "odam_detr_create: bad sizes");
     if (cfg->dtype != 0 && cfg->dtype != 1) return odam_fail(1, "odam_detr_create: dtype must be 0 (fp32) or 1 (bf16)");
+    if (cfg->basic_block != 0 && cfg->basic_block != 1) return odam_fail(1, "odam_detr_create: basic_block must be 0 (Bottleneck) or 1 (BasicBlock)");
+    if (cfg->basic_block && cfg->dilation)      // torchvision BasicBlock: "Dilation > 1 not supported in BasicBlock"
+        return odam_fail(3, "odam_detr_create: dilation (DC5) is not supported with BasicBlock backbones (resnet18 / resnet34)");
+    for (int l = 0; l < 4; l++)
+        if (cfg->resnet_blocks[l] < 1) return odam_fail(1, "odam_detr_create: every ResNet stage needs at least one block");
     odam_detr* m = new odam_detr();
     m->cfg = *cfg;
+    m->basic = cfg->basic_block != 0;
     m->dt = cfg->dtype;
     m->es = cfg->dtype ? 2 : 4;
     m->H1 = conv_out(cfg->img_h, 7, 2, 3); m->W1 = conv_out(cfg->img_w, 7, 2, 3);
@@ -461,9 +479,32 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
             r.scale = m->stem.scale; r.bias = m->stem.bias;
         }
     }
+    int inplanes = 64;
     for (int l = 0; l < 4; l++) {
         for (int i = 0; i < c.resnet_blocks[l]; i++) {
             const std::string p = bb + "layer" + std::to_string(l + 1) + "." + std::to_string(i) + ".";
+            if (m->basic) {
+                // torchvision BasicBlock (expansion 1): conv1 3x3 / stride, pad 1 -> bn1 -> ReLU; conv2 3x3, pad 1 -> bn2 -> + identity
+                // (or the 1x1 / stride downsample where the stride or the width changes: layer2.0, layer3.0, layer4.0) -> ReLU
+                const int planes = 64 << l, stride = (i == 0 && l > 0) ? 2 : 1;
+                const bool ds = stride != 1 || inplanes != planes;
+                Bottleneck b;
+                NEED(w1, p + "conv1.weight"); NEED(w2, p + "conv2.weight");
+                RC(check_shape(*w1, planes, inplanes, 3, p + "conv1.weight"));
+                RC(check_shape(*w2, planes, planes, 3, p + "conv2.weight"));
+                RC(pack_conv(m, b.c1, *w1, stride, 1)); RC(fold_bn(m, b.c1, p + "bn1"));
+                RC(pack_conv(m, b.c2, *w2, 1, 1)); RC(fold_bn(m, b.c2, p + "bn2"));
+                if (ds) {
+                    NEED(wd, p + "downsample.0.weight");
+                    RC(check_shape(*wd, planes, inplanes, 1, p + "downsample.0.weight"));
+                    RC(pack_conv(m, b.ds, *wd, stride, 0)); RC(fold_bn(m, b.ds, p + "downsample.1"));
+                    b.has_ds = true;
+                }
+                m->blocks.push_back(b);
+                m->block_stride.push_back(stride);
+                inplanes = planes;
+                continue;
+            }
             // `dilation` (backbone.py:89-91 -> torchvision replace_stride_with_dilation = [False, False, True]): layer4's stride
             // becomes a dilation -- its first block runs with stride 1 and the PREVIOUS dilation (1), the others with dilation 2
             // and padding 2 (torchvision ResNet._make_layer: previous_dilation for block 0, self.dilation *= stride after it)
@@ -484,8 +525,14 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
             m->block_stride.push_back(stride);
         }
     }
+    m->l4_ch = m->basic ? m->blocks.back().c2.Cout : m->blocks.back().c3.Cout;
     {
         NEED(w, "input_proj.weight"); NEED(b, "input_proj.bias");
+        if (w->shape.size() != 4 || (int)w->shape[1] != m->l4_ch) {
+            std::snprintf(g_odam_err, sizeof(g_odam_err), "odam_detr_finalize: input_proj.weight must read the layer4 map (%d channels for "
+                          "this backbone)", m->l4_ch);
+            return 1;
+        }
         RC(pack_conv(m, m->input_proj, *w, 1, 0));
         RC(m->upload(&m->input_proj.bias, b->data));
     }
@@ -555,11 +602,22 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
     }
     // workspace (bytes = elements * es)
     const size_t B = c.max_batch, es = m->es;
-    const size_t big = B * m->H2 * m->W2 * 256 * es;
+    size_t big = B * m->H2 * m->W2 * 256 * es, tsz = big / 2;
+    if (m->basic) {
+        // BasicBlock: every tensor of a stage (block output, conv1 output, downsample) has that stage's width at its resolution;
+        // the largest over the stages (and the pooled stem, 64 channels = layer1's) sizes all of them
+        size_t mx = B * m->H2 * m->W2 * 64;
+        int h = m->H2, w = m->W2;
+        for (int l = 1; l < 4; l++) {
+            h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1);
+            mx = std::max(mx, B * h * w * (size_t)(64 << l));
+        }
+        big = tsz = mx * es;
+    }
     RC(m->dev_alloc(&m->x4, B * (c.img_h + 6) * (c.img_w + 8) * (m->dt ? 8 : 4) * es));     // room for the framed fp32 image
     RC(m->dev_alloc(&m->stem_out, B * m->H1 * m->W1 * 64 * es));
     RC(m->dev_alloc(&m->bufA, big)); RC(m->dev_alloc(&m->bufB, big)); RC(m->dev_alloc(&m->dsb, big));
-    RC(m->dev_alloc(&m->t1, big / 2)); RC(m->dev_alloc(&m->t2, big / 2));
+    RC(m->dev_alloc(&m->t1, tsz)); RC(m->dev_alloc(&m->t2, tsz));
     const size_t M = B * m->L, Mq = B * c.num_queries, F = c.dim_feedforward;
     RC(m->dev_alloc(&m->src, M * E * es)); RC(m->dev_alloc(&m->srcpos, M * E * es)); RC(m->dev_alloc(&m->qk, M * 2 * E * es));
     RC(m->dev_alloc(&m->v, M * E * es)); RC(m->dev_alloc(&m->att, M * E * es)); RC(m->dev_alloc(&m->tmp, M * E * es));
@@ -619,7 +677,22 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
     char* tin = m->t1;          // where this block's 1x1 reduce output lives (the 3x3's input)
     char* tout = m->t2;         // the other small buffer: the 3x3's output, or -- chained -- the NEXT block's reduce output
     bool have_c1 = false;       // the previous block's launch already computed this block's reduce
-    for (size_t i = 0; i < m->blocks.size(); i++) {
+    for (size_t i = 0; m->basic && i < m->blocks.size(); i++) {
+        // BasicBlock: conv1 (3x3 / stride) + bn1 + ReLU -> t1; conv2 (3x3) + bn2 + identity or downsample + ReLU in conv2's epilogue
+        const Bottleneck& b = m->blocks[i];
+        const int s = m->block_stride[i];
+        const int Ho = conv_out(H, 3, s, 1), Wo = conv_out(W, 3, s, 1);
+        RC(conv_t(m, b.c1, cur, B, H, W, nullptr, true, tin, st));
+        const char* res = cur;
+        if (b.has_ds) {
+            RC(conv_t(m, b.ds, cur, B, H, W, nullptr, false, m->dsb, st));
+            res = m->dsb;
+        }
+        RC(conv_t(m, b.c2, tin, B, Ho, Wo, res, true, nxt, st));
+        char* t = cur; cur = nxt; nxt = t;
+        H = Ho; W = Wo;
+    }
+    for (size_t i = 0; !m->basic && i < m->blocks.size(); i++) {
         const Bottleneck& b = m->blocks[i];
         const int s = m->block_stride[i];
         const int Ho = conv_out(H, 3, s, 1), Wo = conv_out(W, 3, s, 1);
@@ -755,7 +828,7 @@ extern "C" int odam_detr_forward_masked(odam_detr* m, const float* img, int B, c
 extern "C" int odam_detr_debug_read(odam_detr* m, int B, float* layer4_nchw, float* memory, void* stream) {
     if (!m || !m->finalized || !m->layer4) return odam_fail(1, "odam_detr_debug_read: no forward has run");
     hipStream_t st = (hipStream_t)stream;
-    if (layer4_nchw) RC(odam_dk::launch_nhwc_to_nchw(m->layer4, layer4_nchw, B, m->fh, m->fw, 2048, m->dt, st));
+    if (layer4_nchw) RC(odam_dk::launch_nhwc_to_nchw(m->layer4, layer4_nchw, B, m->fh, m->fw, m->l4_ch, m->dt, st));
     if (memory) RC(odam_dk::launch_to_f32(m->memory_out ? m->memory_out : m->src, memory, (size_t)B * m->L * m->cfg.hidden_dim, m->dt, st));
     return 0;
 }

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import RESNET_BLOCKS
+from .weights import RESNET_BLOCK_TYPE, RESNET_BLOCKS, layer4_channels
 
 
 class _Cfg(ctypes.Structure):
@@ -20,7 +20,7 @@ class _Cfg(ctypes.Structure):
                 ("dim_feedforward", ctypes.c_int), ("enc_layers", ctypes.c_int), ("dec_layers", ctypes.c_int),
                 ("num_queries", ctypes.c_int), ("num_classes1", ctypes.c_int), ("angle_bins", ctypes.c_int),
                 ("max_batch", ctypes.c_int), ("img_h", ctypes.c_int), ("img_w", ctypes.c_int), ("dtype", ctypes.c_int),
-                ("pre_norm", ctypes.c_int), ("dilation", ctypes.c_int)]
+                ("pre_norm", ctypes.c_int), ("dilation", ctypes.c_int), ("basic_block", ctypes.c_int)]
 
 
 def _axis_phase_table(counts, channels, temperature):
@@ -79,6 +79,11 @@ class Detector:
                  dec_layers=6, num_queries=100, num_classes=18, angle_bins=30, max_batch=8, device="cuda:0",
                  n_streams=2, dtype="fp32", pre_norm=False, position_embedding="sine", dilation=False):
         self.n_streams = max(1, int(n_streams))
+        if backbone not in RESNET_BLOCKS:       # backbone.py:90 getattr(torchvision.models, name): the ResNets this library builds
+            raise ValueError(f"backbone={backbone!r}: not supported (one of {', '.join(sorted(RESNET_BLOCKS))})")
+        self.basic_block = RESNET_BLOCK_TYPE[backbone] == "basic"
+        if self.basic_block and dilation:       # torchvision BasicBlock: "Dilation > 1 not supported in BasicBlock"
+            raise ValueError(f"backbone={backbone!r}: dilation (DC5) is not supported with BasicBlock backbones")
         if position_embedding not in ("sine", "v2", "learned", "v3"):      # build_position_encoding (position_encoding.py:77-87)
             raise ValueError(f"not supported {position_embedding}")
         self.learned_pos = position_embedding in ("learned", "v3")
@@ -150,6 +155,7 @@ class Detector:
         cfg.dtype = 1 if self.dtype == "bf16" else 0
         cfg.pre_norm = 1 if self.pre_norm else 0
         cfg.dilation = 1 if self.dilation else 0
+        cfg.basic_block = 1 if self.basic_block else 0
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(L.odam_detr_create(ctypes.byref(cfg), ctypes.byref(h)), "odam_detr_create")
@@ -285,12 +291,13 @@ class Detector:
         return res
 
     def debug_taps(self, B, H, W):
-        """layer4 feature map [B,2048,h,w] and encoder memory [B,h*w,256] of the last forward (tests)."""
+        """layer4 feature map [B,C4,h,w] (C4 = 2048 Bottleneck, 512 BasicBlock backbones) and encoder memory [B,h*w,256] of the
+        last forward (tests)."""
         hd = self._handle(H, W)
         L = _lib.lib()
         fh, fw = ctypes.c_int(), ctypes.c_int()
         L.odam_detr_feature_hw(hd, ctypes.byref(fh), ctypes.byref(fw))
-        l4 = torch.empty(B, 2048, fh.value, fw.value, device=self.device)
+        l4 = torch.empty(B, layer4_channels(self.arch["backbone"]), fh.value, fw.value, device=self.device)
         mem = torch.empty(B, fh.value * fw.value, self.arch["hidden_dim"], device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(L.odam_detr_debug_read(hd, B, _lib.ptr(l4), _lib.ptr(mem),
@@ -481,8 +488,13 @@ def build(args):
     num_classes = 18 if ds == "scan_net" else (91 if ds == "coco" else 20)
     if g("masks", False):
         raise _lib.OdamError("the segmentation head (masks) is not part of this path")
+    backbone = g("backbone", "resnet50")
+    if backbone.startswith(("resnext", "wide_resnet")):
+        raise _lib.OdamError(f"backbone={backbone!r}: grouped / widened ResNet variants are not built (resnet18/34/50/101/152 are)")
+    if backbone in RESNET_BLOCK_TYPE and RESNET_BLOCK_TYPE[backbone] == "basic" and g("dilation", False):
+        raise _lib.OdamError(f"backbone={backbone!r}: dilation (DC5) is not supported with BasicBlock backbones")
     det = Detector(pre_norm=g("pre_norm", False), position_embedding=g("position_embedding", "sine"), dilation=g("dilation", False),
-                   backbone=g("backbone", "resnet50"), hidden_dim=g("hidden_dim", 256), nheads=g("nheads", 8),
+                   backbone=backbone, hidden_dim=g("hidden_dim", 256), nheads=g("nheads", 8),
                    dim_feedforward=g("dim_feedforward", 2048), enc_layers=g("enc_layers", 6),
                    dec_layers=g("dec_layers", 6), num_queries=g("num_queries", 100), num_classes=num_classes)
     return det, None, None

@@ -2,14 +2,23 @@
 (the trained checkpoints of the reference are a Google-Drive download, README.md:13 -- not available
 offline).  Same generator on every box: torch's CPU Philox/MT streams are version-stable.
 
-Scaling keeps activations O(1) through the 16/33 bottlenecks (He-uniform filters, residual branch
-damped through bn3.weight) and spreads the class logits so that some queries clear the 0.6 detection
+Scaling keeps activations O(1) through the 8-50 residual blocks (He-uniform filters, residual branch
+damped through its last batch norm: bn3.weight of a bottleneck, bn2.weight of a basic block) and spreads the class logits so that some queries clear the 0.6 detection
 threshold, which exercises post-processing, NMS and everything downstream."""
 import math
 
 import torch
 
-RESNET_BLOCKS = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3)}
+RESNET_BLOCKS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3), "resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3),
+                 "resnet152": (3, 8, 36, 3)}
+# torchvision's block type per model (src/models/backbone.py:90 builds whichever ResNet the config names): BasicBlock = two 3x3
+# convolutions, expansion 1 (layer4 has 512 channels); Bottleneck = 1x1 reduce, 3x3, 1x1 expand, expansion 4 (2048)
+RESNET_BLOCK_TYPE = {"resnet18": "basic", "resnet34": "basic", "resnet50": "bottleneck", "resnet101": "bottleneck",
+                     "resnet152": "bottleneck"}
+
+
+def layer4_channels(backbone):
+    return 512 if RESNET_BLOCK_TYPE[backbone] == "basic" else 2048
 
 
 def _u(gen, shape, bound):
@@ -86,6 +95,8 @@ def scene_transformer(sd, enc_layers=6, dec_layers=6):
 def _scene_heads(sd, backbone, seed, num_classes, enc_layers=6, dec_layers=6):
     import os
     import numpy as np
+    if RESNET_BLOCK_TYPE[backbone] != "bottleneck":
+        raise ValueError(f"scene weights: no batch-norm calibration for the {backbone} body (bottleneck backbones only)")
     scene_backbone_gains(sd)
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", f"synth_calib_{backbone}_s{seed}.npz")
     if not os.path.exists(path):
@@ -124,10 +135,22 @@ def _make_state_dict(backbone, hidden, ffn, enc_layers, dec_layers, num_queries,
     sd[bb + "conv1.weight"] = _conv(g, 64, 3, 7)
     _bn(sd, bb + "bn1", g, 64)
     inplanes = 64
+    basic = RESNET_BLOCK_TYPE[backbone] == "basic"
     for l, nb in enumerate(RESNET_BLOCKS[backbone]):
         planes = 64 * 2 ** l
         for i in range(nb):
             p = f"{bb}layer{l + 1}.{i}."
+            if basic:
+                # torchvision BasicBlock: conv1 3x3 (stride on the first block of layers 2-4), conv2 3x3; a downsample only where
+                # the stride or the width changes (expansion 1: layer1.0 has none)
+                stride = 2 if (i == 0 and l > 0) else 1
+                sd[p + "conv1.weight"] = _conv(g, planes, inplanes, 3); _bn(sd, p + "bn1", g, planes)
+                sd[p + "conv2.weight"] = _conv(g, planes, planes, 3); _bn(sd, p + "bn2", g, planes, gain=0.4)
+                if stride != 1 or inplanes != planes:
+                    sd[p + "downsample.0.weight"] = _conv(g, planes, inplanes, 1)
+                    _bn(sd, p + "downsample.1", g, planes, gain=0.7)
+                inplanes = planes
+                continue
             sd[p + "conv1.weight"] = _conv(g, planes, inplanes, 1); _bn(sd, p + "bn1", g, planes)
             sd[p + "conv2.weight"] = _conv(g, planes, planes, 3); _bn(sd, p + "bn2", g, planes)
             sd[p + "conv3.weight"] = _conv(g, planes * 4, planes, 1); _bn(sd, p + "bn3", g, planes * 4, gain=0.4)
