@@ -9,8 +9,11 @@ One "step" = one pass of the hot path over one scene:
   -> all-gather of detections (N > 1) -> super-quadric fit of this rank's objects, twice (run_processor.py:81-83
   runs optim -> merge -> optim; the merge itself is outside the hot path) -> all-gather of fitted parameters.
 value = frames of the WHOLE scene x steps / wall time (max over ranks).  Strong scaling: the scene is fixed.
+A plain run does set-up, warm-up, the timed steps, the dumps asked for and the line; --full adds the figures that take
+passes of their own (kernel rooflines, other precisions and configurations, the whole driver chain, the CPU baseline).
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full   # + every secondary figure (roofline, configs[3], CPU baseline, ...)
   python bench.py --gpus N --steps K --warmup W          # no WORLD_SIZE in the environment: this process starts the N ranks itself
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W          # ... or an external launcher does (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*)
@@ -175,9 +178,13 @@ def main():
                     "frames, 38 beyond)")
     ap.add_argument("--streams", type=int, default=0, help="concurrent HIP streams; 0 = by shard size")
     ap.add_argument("--chunk", type=int, default=0, help="frames per device->host copy of detections; 0 = 4 batches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary blocks (host-resident frames, shard of 8, with association)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE configs[3] block (R101, bf16, 50 objects)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure every figure beside it in passes of its own: roofline, "
+                    "attention and fit kernels, the fp32-matrix-instruction pass, detection alone, the secondary blocks, --full-chain, configs[3], "
+                    "the CPU baseline (the --no-* switches below leave parts out); without it a run is set-up, warm-up, the timed steps, "
+                    "--dump / --dump-outputs and the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary blocks (host-resident frames, shard of 8, with association)")
+    ap.add_argument("--no-config4", action="store_true", help="--full: skip the BASELINE configs[3] block (R101, bf16, 50 objects)")
     ap.add_argument("--config4-streams", type=int, default=3, help="HIP streams of the configs[3] block")
     ap.add_argument("--config4-batch", type=int, default=76, help="frames per forward of the configs[3] block")
     ap.add_argument("--config4-frames", type=int, default=1000, help="frames of the configs[3] scene")
@@ -189,7 +196,7 @@ def main():
     ap.add_argument("--native-collectives", action="store_true", help="both all-gathers through the library's own RCCL communicator "
                     "(include/odam_comm.h: odam_allgather_detections) instead of torch.distributed")
     ap.add_argument("--dump", default="", help="rank 0 writes the gathered detections and fitted rows of the last step here (.npz)")
-    ap.add_argument("--full-chain", action="store_true", default=True, help="secondary block (on by default): the whole driver chain of "
+    ap.add_argument("--full-chain", action="store_true", default=True, help="secondary block (on by default under --full): the whole driver chain of "
                     "run_processor.py:70-83 on the ranks of this job (detect shard -> all-gather -> association replayed on every rank -> fit of "
                     "the RESULTING tracks -> merge -> fit; odam_amd/pipeline.py)")
     ap.add_argument("--no-full-chain", dest="full_chain", action="store_false")
@@ -342,29 +349,7 @@ def main():
         n_det, fitted = step()
     sync()
     dt = time.perf_counter() - t0
-    dump = dict(last, fitted=fitted)        # the timed region's result (later passes below run other modes)
-    det_phase_ms = sum(a.elapsed_time(b) for a, b in det_ms)
-    # the contraction kernel alone on the device: one more forward on one stream with an event pair around
-    # every launch (flop count per launch comes from the library)
-    detector.profile(H, W, True)
-    detector(detector.preprocess_u8(frames[:args.batch]))
-    torch.cuda.synchronize()
-    n_launch, conv_ms, conv_flops = detector.profile_read(H, W)
-    att_n, att_ms, att_flops = detector.profile_read_attention(H, W)
-    detector.profile(H, W, False)
-    # the same scene with every fp32 layer on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32): one untimed + one timed pass
-    split_mode = _lib.config()["cg.f32"] == 2
-    f32_instr = None
-    if split_mode and rank == 0 and ws == 1:
-        _lib.check(_lib.lib().odam_op_conv_f32_mode(0), "odam_op_conv_f32_mode")
-        step(); torch.cuda.synchronize()
-        s0 = time.perf_counter(); step(); torch.cuda.synchronize()
-        f32_instr = N / (time.perf_counter() - s0)
-        _lib.check(_lib.lib().odam_op_conv_f32_mode(2), "odam_op_conv_f32_mode")
-    secondary = {}
-    if rank == 0 and ws == 1 and not args.no_secondary:
-        secondary = secondary_blocks(step, detector, args.chunk, frames, tracks, N, dump["per_frame"], scene, device, dt / args.steps,
-                                     det_phase_ms / args.steps, last)
+    dump = dict(last, fitted=fitted)        # the timed region's result (the --full passes below run other modes)
     if args.dump and rank == 0:
         np.savez(args.dump, blk=dump["blk"], cnt=dump["cnt"], fitted=dump["fitted"])
     if args.dump_outputs and rank == 0:
@@ -378,12 +363,7 @@ def main():
         t = torch.tensor([dt], device=device if args.backend == "nccl" else "cpu", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-
-    # stage split (informational): one more untimed scene with explicit timers
-    torch.cuda.synchronize(); s0 = time.perf_counter()
-    for _ in detector.detect_resident_chunks(frames, img_size, K, chunk=args.chunk, batch=BATCH):
-        pass
-    torch.cuda.synchronize(); t_det = time.perf_counter() - s0
+    split_mode = _lib.config()["cg.f32"] == 2
 
     result = {
         "metric": "frames/sec end-to-end (DETR detect + SQ fit), 640x480 ScanNet, 1/2/4/8 GPU",
@@ -407,8 +387,6 @@ def main():
                         "own chain 1.1-1.9e-7 (tests/native/x3_probe.hip); every parity test passes unchanged in this mode; "
                         "smaller layers take the same six products on 64- / 128-row tiles (cg.small_x3; layers whose input channels "
                         "are not a multiple of 32 stay on v_mfma_f32_32x32x2_f32)") if split_mode else "v_mfma_f32_32x32x2_f32 (ODAM_CG_BIG_F32=0)",
-        "fp32_matrix_instruction_only": ({"value": f32_instr, "unit": "frames/s", "note": "same scene, one timed pass with "
-                                          "odam_op_conv_f32_mode(0): every layer on v_mfma_f32_32x32x2_f32"} if f32_instr else None),
         "data": "synthetic (seeded 640x480 uint8 RGB stream resident in HBM, put through the reference transform on the "
                 "device inside the step; deterministic random-init DETR-R50 weights; synthetic 82-column object tracks "
                 "for the SQ fit)",
@@ -421,8 +399,47 @@ def main():
         "library_config": _lib.config(),      # every kernel-selecting switch in force (include/odam_config.h); defaults unless ODAM_CONFIG says otherwise
         "detections_per_scene": n_det,
         "detections_per_frame": n_det / N,
-        "detect_only_frames_per_s_per_gpu": (f1 - f0) / t_det,
+        "full": args.full,
     }
+    if not args.full:
+        # a plain run ends with its headline: every figure below takes passes of its own beside the timed steps
+        if ws > 1 or args.force_collectives:
+            torch.distributed.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result))
+        return
+
+    det_phase_ms = sum(a.elapsed_time(b) for a, b in det_ms)
+    # the contraction kernel alone on the device: one more forward on one stream with an event pair around
+    # every launch (flop count per launch comes from the library)
+    detector.profile(H, W, True)
+    detector(detector.preprocess_u8(frames[:args.batch]))
+    torch.cuda.synchronize()
+    n_launch, conv_ms, conv_flops = detector.profile_read(H, W)
+    att_n, att_ms, att_flops = detector.profile_read_attention(H, W)
+    detector.profile(H, W, False)
+    # the same scene with every fp32 layer on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32): one untimed + one timed pass
+    f32_instr = None
+    if split_mode and rank == 0 and ws == 1:
+        _lib.check(_lib.lib().odam_op_conv_f32_mode(0), "odam_op_conv_f32_mode")
+        step(); torch.cuda.synchronize()
+        s0 = time.perf_counter(); step(); torch.cuda.synchronize()
+        f32_instr = N / (time.perf_counter() - s0)
+        _lib.check(_lib.lib().odam_op_conv_f32_mode(2), "odam_op_conv_f32_mode")
+    secondary = {}
+    if rank == 0 and ws == 1 and not args.no_secondary:
+        secondary = secondary_blocks(step, detector, args.chunk, frames, tracks, N, dump["per_frame"], scene, device, dt / args.steps,
+                                     det_phase_ms / args.steps, last)
+
+    # stage split (informational): one more untimed scene with explicit timers
+    torch.cuda.synchronize(); s0 = time.perf_counter()
+    for _ in detector.detect_resident_chunks(frames, img_size, K, chunk=args.chunk, batch=BATCH):
+        pass
+    torch.cuda.synchronize(); t_det = time.perf_counter() - s0
+
+    result["fp32_matrix_instruction_only"] = ({"value": f32_instr, "unit": "frames/s", "note": "same scene, one timed pass with "
+                                              "odam_op_conv_f32_mode(0): every layer on v_mfma_f32_32x32x2_f32"} if f32_instr else None)
+    result["detect_only_frames_per_s_per_gpu"] = (f1 - f0) / t_det
     result.update(secondary)
     result["parity"] = parity_block()
     pmc = pmc_summary()

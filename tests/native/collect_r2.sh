@@ -7,7 +7,7 @@ prof() {  # name, then the python script + args
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/r2c_$name -o t -- python3 "$@" > $O/r2c_$name.log 2>&1
 }
-prof bench $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-config4
+prof bench $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-config4
 prof detr_f32 $R/tests/native/prof_detr1.py 32 fp32 resnet50
 python3 $R/tests/native/analyze_trace.py $O/r2c_detr_f32/t_kernel_trace.csv 32 2 resnet50 > $O/r2c_detr_f32_per_layer.txt 2>&1
 export ODAM_CG_BIG_F32=0
@@ -33,4 +33,4 @@ ODAM_ASSOC_PERSIST=0 python3 tests/native/perf_assoc.py > $O/r2c_perf_assoc_laun
 ./tests/native/ring_stamps1 > $O/r2c_ring_stamps.txt 2>&1
 bash tests/native/run_pmc.sh
 cp $O/pmc_summary.json $R/profiles/pmc_summary.json 2>/dev/null
-python3 bench.py --steps 3 --warmup 1 > $O/r2c_bench_line.json 2> $O/r2c_bench_line.err
+python3 bench.py --full --steps 3 --warmup 1 > $O/r2c_bench_line.json 2> $O/r2c_bench_line.err
