@@ -133,6 +133,11 @@ int odam_op_conv2d_nhwc(const float* x, const float* w_packed, const float* scal
 int odam_op_conv2d_nhwc_bf16(const void* x, const void* w_packed, const float* scale, const float* bias,
                              const void* residual, void* y, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                              int stride, int pad, int Kpad, int relu, int out_f32, int k_order, void* stream);
+/* the same entry with dilation (dil >= 1: tap (ky, kx) reads input pixel (oy stride - pad + ky dil, ox stride - pad + kx dil)) for both
+ * operand types: dtype 0 = fp32 (x, w_packed, residual, y float32; out_f32 must be 0), 1 = bf16 as odam_op_conv2d_nhwc_bf16 */
+int odam_op_conv2d_nhwc_ex(const void* x, const void* w_packed, const float* scale, const float* bias, const void* residual,
+                           void* y, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                           int Kpad, int relu, int k_order, int dtype, int out_f32, void* stream);
 /* bf16 bottleneck tail as one launch (BASELINE config 4; replaces what torchvision's Bottleneck.forward runs after conv1 --
  * conv2, bn2, relu, conv3, bn3, += identity, relu -- as instantiated at src/models/backbone.py:90-92, plus optionally the next
  * block's conv1 / bn1 / relu): x [dev][B,H,W,P] bf16 (P = 64 / 128 / 256), w2 [P][9 P] packed k_order 1, w3 [4 P][P], residual / y
@@ -141,6 +146,36 @@ int odam_op_conv2d_nhwc_bf16(const void* x, const void* w_packed, const float* s
 int odam_op_bottleneck_bf16(const void* x, const void* w2, const float* s2, const float* b2, const void* w3, const float* s3,
                             const float* b3, const void* residual, void* y, const void* w1n, const float* s1n, const float* b1n,
                             void* y_next, int B, int H, int W, int P, int stride, int PN, void* stream);
+/* fp32 bottleneck tail as one launch (fp32 split mode, odam_op_conv_f32_mode 2): the same operation and layouts in float32 for P = 64
+ * (PN = 0 / 64 / 128) and P = 128 (PN = 0); the packed fp32 filters are split into bf16 planes on the host for the call (synchronous).
+ * Returns 4 where the fused kernel does not apply (shape, size, configuration).  The 3x3's output is the bits odam_op_conv2d_nhwc
+ * returns for it; y and y_next differ from the separate launches only through the summation order of the expand / reduce. */
+int odam_op_bottleneck_f32(const float* x, const float* w2, const float* s2, const float* b2, const float* w3, const float* s3,
+                           const float* b3, const float* residual, float* y, const float* w1n, const float* s1n, const float* b1n,
+                           float* y_next, int B, int H, int W, int P, int stride, int PN, void* stream);
+/* Which kernel each contraction ran on (host-side log, no device work, no synchronisation): one token per call of the contraction
+ * launcher since the last reset, in launch order, noted where the kernel is chosen.  buf [host][n] receives them '\n'-separated
+ * (the newest 4096 if more were noted; as many as fit); returns how many were noted since the reset (-1: n <= 0); reset != 0
+ * starts a new log.  buf may be null (count / reset only).  Tokens (a bottleneck launch counts once, whatever number of image
+ * groups it runs as):
+ *   small tiles   <f32|bf16>.small.<BM>x<BN>.w<waves>[.ut][.x3][.s4]    .ut: LDS-DMA uniform-tap gather (else register-staged),
+ *                 .x3: fp32 operands split in registers onto the bf16 instruction (else v_mfma_f32_32x32x2_f32), .s4: four LDS stages
+ *   ring kernel   f32.ring.m<2|3|4>.<rows>x<cols>[.pool]   m2 split in registers, m3 pre-split filters 32x32x16, m4 pre-split 16x16x32;
+ *                 bf16.ring.<rows>x<cols>[.pool]           .pool: conv1 with the max-pool on its tile
+ *   bottleneck    f32.fused.m<3|4>.<l1|chain64|chain128|l2>   l1: 64-channel 3x3 + expand, chain64 / chain128: + the next reduce,
+ *                 bf16.fused.p<P>[.chain<PN>]                 l2: 128-channel 3x3 + expand
+ * The fp32 tokens, all of them (tests/test_conv_f32_gpu.py covers each):
+ *   FP32-TOKENS-BEGIN
+ *   f32.small.128x64.w4 f32.small.128x64.w4.ut f32.small.128x64.w4.ut.x3 f32.small.128x64.w8 f32.small.128x64.w8.ut
+ *   f32.small.128x64.w8.ut.x3 f32.small.64x64.w4 f32.small.64x64.w4.ut f32.small.64x64.w4.ut.x3 f32.small.64x64.w4.ut.s4
+ *   f32.small.64x64.w4.ut.x3.s4 f32.small.128x128.w4 f32.small.128x128.w4.ut f32.small.128x128.w4.ut.x3 f32.small.128x128.w8
+ *   f32.small.128x128.w8.ut f32.small.128x128.w8.ut.x3
+ *   f32.ring.m2.256x64 f32.ring.m2.256x128 f32.ring.m2.256x256 f32.ring.m3.256x64 f32.ring.m3.256x128 f32.ring.m3.256x256
+ *   f32.ring.m4.256x64 f32.ring.m4.256x128 f32.ring.m4.256x256 f32.ring.m4.512x64 f32.ring.m4.512x64.pool
+ *   f32.fused.m3.l1 f32.fused.m3.chain64 f32.fused.m3.chain128 f32.fused.m3.l2 f32.fused.m4.l1 f32.fused.m4.chain64
+ *   f32.fused.m4.chain128 f32.fused.m4.l2
+ *   FP32-TOKENS-END */
+long long odam_op_conv_paths(char* buf, int n, int reset);
 /* which layers the bf16-native 256-row schedule of the contraction kernel takes: 0 none, 1 those large enough to fill
  * the device (default), 2 every eligible layer (parity tests on small shapes).  Process-wide; also ODAM_CG_BIG. */
 int odam_op_conv_bf16_mode(int mode);

@@ -4,6 +4,7 @@
 namespace odam_cg {
 
 int launch_big_bf16(int bn, int nth, const ConvGemmArgs& a, hipStream_t stream) {
+    note_path("bf16.ring.%dx%d%s", big_bm(bn, nth), bn, a.pool ? ".pool" : "");
     if (nth == 1024) {
         if (bn == 256) return launch_big<0, 256, 4, 1024>(a, stream);
         if (bn == 64) return launch_big<0, 64, 4, 1024>(a, stream);

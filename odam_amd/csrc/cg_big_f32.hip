@@ -4,6 +4,7 @@
 namespace odam_cg {
 
 int launch_big_f32(int mode, int bn, int nth, const ConvGemmArgs& a, hipStream_t stream) {
+    note_path("f32.ring.m%d.%dx%d%s", mode, big_bm(bn, nth), bn, a.pool ? ".pool" : "");
     if (nth == 1024) {
         if (mode == 4 && bn == 64) return launch_big<4, 64, 4, 1024>(a, stream);
     } else if (bn == 256) {

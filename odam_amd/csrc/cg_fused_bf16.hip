@@ -18,6 +18,8 @@ static int launch_fused_bf16_as(const ConvGemmArgs& a, hipStream_t stream) {
 }
 int launch_fused_bf16(const ConvGemmArgs& a, hipStream_t stream) {
     const int pn = a.G_Wt ? a.G_N : 0;
+    if (pn) note_path("bf16.fused.p%d.chain%d", a.Cout, pn);
+    else note_path("bf16.fused.p%d", a.Cout);
     if (a.Cout == 64 && pn == 0) return launch_fused_bf16_as<64, 5>(a, stream);
     if (a.Cout == 64 && pn == 64) return launch_fused_bf16_as<64, 6>(a, stream);
     if (a.Cout == 64 && pn == 128) return launch_fused_bf16_as<64, 7>(a, stream);

@@ -1,6 +1,8 @@
 // cg_fused_f32.hip -- layer1 / layer2 bottlenecks as one launch, fp32 split mode.  See cg_big.hpp, cg_tails_f32.hpp.
 #include "cg_big.hpp"
 
+#include <algorithm>
+
 namespace odam_cg {
 
 template <int MODE>
@@ -23,7 +25,27 @@ static int launch_big_fused_as(const ConvGemmArgs& a, hipStream_t stream) {
 int launch_big_fused(const ConvGemmArgs& a, hipStream_t stream) {
     const int m16 = odam_cfg::get(odam_cfg::CG_MFMA16);      // 2: the 128-column bottleneck launches too, 3: the 64-column ones as well
     const bool x16 = a.Kpad % 32 == 0 && (m16 >= 3 || (m16 == 2 && a.Cout == 128));
-    return x16 ? launch_big_fused_as<4>(a, stream) : launch_big_fused_as<3>(a, stream);
+    note_path("f32.fused.m%d.%s", x16 ? 4 : 3, a.Cout == 128 ? "l2" : !a.G_Wt3 ? "l1" : a.G_N == 128 ? "chain128" : "chain64");
+    // The tails address the residual and the output through buffer descriptors with 31-bit byte offsets from F_res / F_C.  A batch
+    // whose output reaches 2 GiB (layer1 from 40 frames of 800 x 1066) runs as one launch per group of whole images, with the
+    // pointers offset to the group's first image: a row's products, order and roundings do not depend on the tile it falls in,
+    // so the bits are those of one launch -- and the kernel choice stays the same whatever the batch (cg.pin).
+    const long img_rows = (long)a.Ho * a.Wo, img_bytes = img_rows * a.F_ldc * 4;
+    const int group = (int)std::min<long>(a.B, (0x7fffffffL - 1) / img_bytes);      // fused_second_ok: one image fits
+    if (group < 1) return odam_fail(1, "conv_gemm: fused bottleneck: one image's output exceeds 2 GiB");
+    const long lda = a.lda > 0 ? a.lda : a.Cin;
+    for (int b0 = 0; b0 < a.B; b0 += group) {
+        ConvGemmArgs g = a;
+        g.B = std::min(group, a.B - b0);
+        g.M = (int)(g.B * img_rows);
+        g.A = reinterpret_cast<const float*>(a.A) + (size_t)b0 * a.H * a.W * lda;
+        if (a.F_res) g.F_res = a.F_res + (size_t)b0 * img_rows * a.F_ldc;
+        g.F_C = a.F_C + (size_t)b0 * img_rows * a.F_ldc;
+        if (a.G_C) g.G_C = a.G_C + (size_t)b0 * img_rows * a.G_N;
+        const int rc = x16 ? launch_big_fused_as<4>(g, stream) : launch_big_fused_as<3>(g, stream);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 }  // namespace odam_cg

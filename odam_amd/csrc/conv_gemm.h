@@ -110,4 +110,12 @@ bool fused_bf16_ok(const ConvGemmArgs& a);
 // host: exact three-way bf16 split (truncation) of packed fp32 filters w[Cout][Kpad] (Kpad % 16 == 0) into the Wt3 layout
 void split3_filters(const float* w, int Cout, int Kpad, unsigned short* out);
 
+// kernel-choice log (include/odam_detr.h odam_op_conv_paths): one token per launch_conv_gemm call, noted by the launcher that
+// chose the kernel.  Host only (a mutex and a bounded ring of PATH_LOG_N tokens); no device work, no synchronisation.
+constexpr int PATH_LOG_N = 4096, PATH_TOKEN_LEN = 40;
+void note_path(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// '\n'-joined tokens noted since the last reset (the newest PATH_LOG_N of them) into buf [n]; returns how many were noted
+// (more than the buffer shows when the ring wrapped or buf was too short), or -1 for a bad buffer
+long long read_paths(char* buf, int n, int reset);
+
 }  // namespace odam_cg

@@ -4,7 +4,48 @@
 #include "cg_common.hpp"
 #include "cg_launch.h"
 
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+
 namespace odam_cg {
+
+// ---- kernel-choice log ----------------------------------------------------------------------------------------------
+static std::mutex g_path_mu;
+static char g_path_ring[PATH_LOG_N][PATH_TOKEN_LEN];
+static long long g_path_head = 0, g_path_base = 0;      // tokens noted since load / at the last reset
+
+void note_path(const char* fmt, ...) {
+    char tok[PATH_TOKEN_LEN];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(tok, sizeof(tok), fmt, ap);
+    va_end(ap);
+    std::lock_guard<std::mutex> lk(g_path_mu);
+    memcpy(g_path_ring[g_path_head % PATH_LOG_N], tok, sizeof(tok));
+    g_path_head++;
+}
+
+long long read_paths(char* buf, int n, int reset) {
+    std::lock_guard<std::mutex> lk(g_path_mu);
+    const long long noted = g_path_head - g_path_base;
+    if (buf) {
+        if (n <= 0) return -1;
+        int used = 0;
+        buf[0] = 0;
+        for (long long i = std::max(g_path_base, g_path_head - PATH_LOG_N); i < g_path_head; i++) {
+            const char* t = g_path_ring[i % PATH_LOG_N];
+            const int len = (int)strlen(t);
+            if (used + len + 2 > n) break;
+            if (used) buf[used++] = '\n';
+            memcpy(buf + used, t, len + 1);
+            used += len;
+        }
+    }
+    if (reset) g_path_base = g_path_head;
+    return noted;
+}
 
 // NST: LDS stages.  2 = one tile in flight under the tile being multiplied (two workgroups per CU hide the rest).
 // 4 (UT only; small, latency-bound problems that leave most CUs with one workgroup): three tiles in flight, retired
@@ -395,6 +436,8 @@ static int launch_cfg(const ConvGemmArgs& a, hipStream_t stream) {
     const bool ut = odam_cfg::get(odam_cfg::CG_UT) != 0 && a.Cin % (bf ? 64 : 32) == 0 && a.KH * a.KW <= 32 && span * esz < 0x7fffffffL &&
                     (long)a.Cout * a.Kpad * esz < 0x7fffffffL;
     const dim3 g(tiles), b(64 * WM * WN);
+    const bool x3 = !bf && ut && g_big_f32 == 2 && odam_cfg::get(odam_cfg::CG_SMALL_X3) != 0;
+    note_path("%s.small.%dx%d.w%d%s%s%s", bf ? "bf16" : "f32", BM, BN, WM * WN, ut ? ".ut" : "", x3 ? ".x3" : "", ut && NST_UT == 4 ? ".s4" : "");
     if (bf) {
         if (ut) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, true, true, NST_UT>), g, b, 0, stream, a);
         else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, true, false>), g, b, 0, stream, a);
@@ -402,7 +445,7 @@ static int launch_cfg(const ConvGemmArgs& a, hipStream_t stream) {
         // fp32 split mode reaches the layers too small for the ring kernel as well (cg.small_x3): the same six exact products on
         // v_mfma_f32_32x32x16_bf16, both operands split in registers.  Forward of 2 / 8 / 16 frames 4.89 -> 4.59 / 10.24 -> 9.66 /
         // 17.36 -> 16.84 ms (same box, A/B by config); a batch of 32 has few such layers left (30.45 -> 30.32)
-        if (ut && g_big_f32 == 2 && odam_cfg::get(odam_cfg::CG_SMALL_X3) != 0)
+        if (x3)
             hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, true, NST_UT, true>), g, b, 0, stream, a);
         else if (ut) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, true, NST_UT>), g, b, 0, stream, a);
         else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, false>), g, b, 0, stream, a);
@@ -418,7 +461,9 @@ bool fused_second_ok(const ConvGemmArgs& a) {
     if (!a.F_Wt3 || !a.F_C || !a.Wt3 || a.Kpad % 16 != 0) return false;
     const bool l1 = a.Cout == 64 && a.F_ldc == 256, l2 = a.Cout == 128 && a.F_ldc == 512 && !a.G_Wt3;     // the two shapes built
     if ((!l1 && !l2) || a.dil != 1) return false;
-    if ((long)a.Cout * a.Kpad * 6 >= 0x7fffffffL || (long)a.M * a.F_ldc * 4 >= 0x7fffffffL) return false;      // buffer descriptors over the output / residual
+    // buffer descriptors over the output / residual: 31-bit byte offsets within ONE image (launch_big_fused runs a larger batch as
+    // groups of whole images, so that the choice does not depend on the batch)
+    if ((long)a.Cout * a.Kpad * 6 >= 0x7fffffffL || (long)a.Ho * a.Wo * a.F_ldc * 4 >= 0x7fffffffL) return false;
     if (a.G_Wt3 && (fuse < 2 || !a.G_C || (a.G_N != 64 && a.G_N != 128))) return false;      // fuse 1: second layer only
     return big_eligible(a, a.Cout);
 }

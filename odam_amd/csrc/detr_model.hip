@@ -844,31 +844,53 @@ extern "C" int odam_detr_postprocess(odam_detr* m, const float* logits, const fl
 }
 
 // ---- single-operator entry points -------------------------------------------------------------------
+// Split contraction mode: a model keeps its filters pre-split into three bf16 planes (upload_w3); the op-level entries build them for
+// the one call (download, split on the host, upload), so that the op tests drive the SAME kernels a forward does -- the 16x16x32 loop
+// with its ragged last row tile and ragged last columns -- and not only the layer shapes a DETR happens to have.  *d3 = null where
+// the mode or the shape takes no pre-split filters; the caller frees *d3 after synchronising the stream.
+static int split_filters_for_call(const float* w_packed, int Cout, int Kpad, hipStream_t st, unsigned short** d3, const char* who) {
+    *d3 = nullptr;
+    if (odam_cg::f32_mode() != 2 || Kpad % 16 != 0 || (long)Cout * Kpad * 6 >= 0x7fffffffL) return 0;
+    std::vector<float> hw((size_t)Cout * Kpad);
+    ODAM_HIP(hipStreamSynchronize(st));
+    ODAM_HIP(hipMemcpy(hw.data(), w_packed, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<unsigned short> h3(hw.size() * 3);
+    odam_cg::split3_filters(hw.data(), Cout, Kpad, h3.data());
+    ODAM_HIP(hipMalloc(d3, h3.size() * 2));
+    if (hipMemcpy(*d3, h3.data(), h3.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(*d3); *d3 = nullptr;
+        std::snprintf(g_odam_err, sizeof(g_odam_err), "%s: upload of the split filters failed", who);
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int odam_op_conv2d_nhwc_ex(const void* x, const void* w_packed, const float* scale, const float* bias, const void* residual,
+                                      void* y, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                                      int Kpad, int relu, int k_order, int dtype, int out_f32, void* stream) {
+    if (!x || !w_packed || !y) return odam_fail(1, "odam_op_conv2d_nhwc_ex: null pointer");
+    if (dtype != 0 && dtype != 1) return odam_fail(1, "odam_op_conv2d_nhwc_ex: dtype must be 0 (fp32) or 1 (bf16)");
+    if (dil < 1) return odam_fail(1, "odam_op_conv2d_nhwc_ex: dilation must be >= 1");
+    if (dtype == 0 && out_f32) return odam_fail(1, "odam_op_conv2d_nhwc_ex: out_f32 is for bf16 operands");
+    hipStream_t st = (hipStream_t)stream;
+    Conv c;
+    c.w = const_cast<void*>(w_packed); c.scale = const_cast<float*>(scale); c.bias = const_cast<float*>(bias);
+    c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.stride = stride; c.pad = pad; c.Kpad = Kpad; c.dil = dil;
+    c.k_order = k_order;
+    unsigned short* d3 = nullptr;
+    if (dtype == 0) RC(split_filters_for_call((const float*)w_packed, Cout, Kpad, st, &d3, "odam_op_conv2d_nhwc_ex"));
+    c.w3 = d3;
+    const int rc = run_conv(c, x, B, H, W, residual, relu != 0, y, 0, st, dtype, out_f32);
+    if (d3) { (void)hipStreamSynchronize(st); (void)hipFree(d3); }
+    return rc;
+}
+
 extern "C" int odam_op_conv2d_nhwc(const float* x, const float* w_packed, const float* scale, const float* bias,
                                    const float* residual, float* y, int B, int H, int W, int Cin, int Cout, int KH,
                                    int KW, int stride, int pad, int Kpad, int relu, int k_order, void* stream) {
     if (!x || !w_packed || !y) return odam_fail(1, "odam_op_conv2d_nhwc: null pointer");
-    Conv c;
-    c.w = const_cast<float*>(w_packed); c.scale = const_cast<float*>(scale); c.bias = const_cast<float*>(bias);
-    c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.stride = stride; c.pad = pad; c.Kpad = Kpad;
-    c.k_order = k_order;
-    // Split contraction mode: a model keeps its filters pre-split into three bf16 planes (upload_w3); this op-level entry builds them for the
-    // one call (download, split on the host, upload), so that the op tests drive the SAME kernels a forward does -- the 16x16x32 loop with its
-    // ragged last row tile and ragged last columns -- and not only the layer shapes a DETR happens to have.
-    unsigned short* d3 = nullptr;
-    if (odam_cg::f32_mode() == 2 && Kpad % 16 == 0 && (long)Cout * Kpad * 6 < 0x7fffffffL) {
-        std::vector<float> hw((size_t)Cout * Kpad);
-        ODAM_HIP(hipStreamSynchronize((hipStream_t)stream));
-        ODAM_HIP(hipMemcpy(hw.data(), w_packed, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
-        std::vector<unsigned short> h3(hw.size() * 3);
-        odam_cg::split3_filters(hw.data(), Cout, Kpad, h3.data());
-        ODAM_HIP(hipMalloc(&d3, h3.size() * 2));
-        if (hipMemcpy(d3, h3.data(), h3.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d3); return odam_fail(1, "odam_op_conv2d_nhwc: upload of the split filters failed"); }
-        c.w3 = d3;
-    }
-    const int rc = run_conv(c, x, B, H, W, residual, relu != 0, y, 0, (hipStream_t)stream);
-    if (d3) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(d3); }
-    return rc;
+    return odam_op_conv2d_nhwc_ex(x, w_packed, scale, bias, residual, y, B, H, W, Cin, Cout, KH, KW, stride, pad, 1, Kpad, relu,
+                                  k_order, 0, 0, stream);
 }
 
 extern "C" int odam_op_conv2d_nhwc_bf16(const void* x, const void* w_packed, const float* scale, const float* bias,
@@ -903,6 +925,47 @@ extern "C" int odam_op_bottleneck_bf16(const void* x, const void* w2, const floa
     if (!odam_cg::fused_bf16_ok(a)) return odam_fail(4, "odam_op_bottleneck_bf16: the fused kernel does not apply to this shape");
     return odam_cg::launch_conv_gemm(a, (hipStream_t)stream);
 }
+
+// The fp32 counterpart (conv_gemm.hip fused_second_ok / launch_big_fused, split mode): 3x3 (P = 64 or 128 channels, stride 1 or 2,
+// pad 1; w2 [P][9 P] packed k_order 1) + scale / bias / ReLU, 1x1 expand to 4 P + scale / bias (+ residual) + ReLU -> y, and for
+// P = 64 optionally the next reduce (PN = 64 / 128) -> y_next.  The filters come packed in fp32 and are split on the host for the
+// call, as odam_op_conv2d_nhwc does.  Returns 4 where fused_second_ok refuses the shape or the configuration.
+extern "C" int odam_op_bottleneck_f32(const float* x, const float* w2, const float* s2, const float* b2, const float* w3,
+                                      const float* s3, const float* b3, const float* residual, float* y, const float* w1n,
+                                      const float* s1n, const float* b1n, float* y_next, int B, int H, int W, int P, int stride,
+                                      int PN, void* stream) {
+    if (!x || !w2 || !w3 || !y) return odam_fail(1, "odam_op_bottleneck_f32: null pointer");
+    if (PN > 0 && (!w1n || !y_next)) return odam_fail(1, "odam_op_bottleneck_f32: PN > 0 needs w1n and y_next");
+    if (P != 64 && P != 128) return odam_fail(4, "odam_op_bottleneck_f32: the fused kernel is built for P = 64 and 128");
+    hipStream_t st = (hipStream_t)stream;
+    ConvGemmArgs a{};
+    a.dtype = 0;
+    a.A = x; a.Wt = w2; a.scale = s2; a.bias = b2;
+    a.B = B; a.H = H; a.W = W; a.Cin = P; a.log2Cin = ilog2(P);
+    a.Ho = conv_out(H, 3, stride, 1); a.Wo = conv_out(W, 3, stride, 1);
+    a.Cout = P; a.KH = 3; a.KW = 3; a.stride = stride; a.pad = 1; a.Kpad = 9 * P;
+    a.relu = 1; a.M = B * a.Ho * a.Wo; a.ldc = P; a.k_order = 1;
+    a.F_scale = s3; a.F_bias = b3; a.F_res = residual; a.F_C = y; a.F_ldc = 4 * P; a.F_relu = 1;
+    if (PN > 0) { a.G_scale = s1n; a.G_bias = b1n; a.G_C = y_next; a.G_N = PN; }
+    // what fused_second_ok checks before the filters exist: non-null placeholders, then the real split planes
+    a.Wt3 = w2; a.F_Wt3 = w3; a.G_Wt3 = PN > 0 ? w1n : nullptr;
+    if (!odam_cg::fused_second_ok(a)) return odam_fail(4, "odam_op_bottleneck_f32: the fused kernel does not apply to this shape");
+    unsigned short *d2 = nullptr, *d3 = nullptr, *d1 = nullptr;
+    int rc = split_filters_for_call(w2, P, 9 * P, st, &d2, "odam_op_bottleneck_f32");
+    if (!rc) rc = split_filters_for_call(w3, 4 * P, P, st, &d3, "odam_op_bottleneck_f32");
+    if (!rc && PN > 0) rc = split_filters_for_call(w1n, PN, 4 * P, st, &d1, "odam_op_bottleneck_f32");
+    if (!rc) {
+        a.Wt3 = d2; a.F_Wt3 = d3; a.G_Wt3 = PN > 0 ? d1 : nullptr;
+        rc = odam_cg::launch_conv_gemm(a, st);
+    }
+    (void)hipStreamSynchronize(st);
+    if (d2) (void)hipFree(d2);
+    if (d3) (void)hipFree(d3);
+    if (d1) (void)hipFree(d1);
+    return rc;
+}
+
+extern "C" long long odam_op_conv_paths(char* buf, int n, int reset) { return odam_cg::read_paths(buf, n, reset); }
 
 // experiment switch of the bf16-native contraction kernel (conv_gemm.h set_big_mode): 0 off, 1 auto, 2 whenever eligible
 extern "C" int odam_op_conv_bf16_mode(int mode) {

@@ -37,13 +37,41 @@ def frozen_bn(x, sd, p):
     return x * scale + bias
 
 
+# Teacher forcing of the fp32 mode (tests/test_conv_f32_gpu.py): when F32_TRACE is a list, every contraction of detr_forward appends a
+# record in TRACE's format (below; plus `dilation`) -- its operands, its folded FrozenBN scale / bias or Linear bias, residual, ReLU and
+# its output -- and every bottleneck block a record of kind "block" that groups its 3x3 (c2), its expand (c3, whose record holds the
+# residual) and the next block's reduce (next_c1, or None) by their indices in the list, so that a fused launch can be fed the
+# oracle's own inputs.  Recording never changes a value the forward computes: a record holds tensors the forward computed anyway,
+# and the only extra work (the attention projections and the attention output, which F.multi_head_attention_forward keeps to
+# itself) is done beside it for the records alone.
+F32_TRACE = None
+
+
+def _rec_conv(name, x, w, bn_p, sd, bias=None, stride=1, padding=0, dilation=1, res=None, relu=False, y=None):
+    if F32_TRACE is None:
+        return None
+    sc, bi = _bn_fold(sd, bn_p) if bn_p is not None else (None, bias)
+    F32_TRACE.append(dict(kind="conv", name=name, x=x, w=w, scale=sc, bias=bi, stride=stride, padding=padding, dilation=dilation,
+                          res=res, relu=relu, y=y, out_f32=True))
+    return len(F32_TRACE) - 1
+
+
+def _rec_lin(name, x, w, b, relu=False, y=None):
+    if F32_TRACE is not None:
+        F32_TRACE.append(dict(kind="linear", name=name, x=x, w=w, scale=None, bias=b, stride=1, padding=0, dilation=1, res=None,
+                              relu=relu, y=y, out_f32=True))
+
+
 def resnet_body(x, sd, blocks=(3, 4, 6, 3), prefix="backbone.0.body.", dilation=False):
     """torchvision ResNet-50/101 v1.5 body (absent from the reference tree; restated from its published definition).  `dilation`:
     replace_stride_with_dilation = [False, False, True] (src/models/backbone.py:89-91) -- layer4 with stride 1, its 3x3 filters
     dilated by 2 (padding 2) from the second block on, the first block at the previous dilation (ResNet._make_layer)."""
+    x0 = x
     x = F.conv2d(x, sd[prefix + "conv1.weight"], None, stride=2, padding=3)
     x = F.relu(frozen_bn(x, sd, prefix + "bn1"))
+    _rec_conv(prefix + "conv1.weight", x0, sd[prefix + "conv1.weight"], prefix + "bn1", sd, stride=2, padding=3, relu=True, y=x)
     x = F.max_pool2d(x, kernel_size=3, stride=2, padding=1)
+    prev_block = None
     for l in range(4):
         for i in range(blocks[l]):
             p = f"{prefix}layer{l + 1}.{i}."
@@ -52,11 +80,23 @@ def resnet_body(x, sd, blocks=(3, 4, 6, 3), prefix="backbone.0.body.", dilation=
             dil = 2 if (dc5 and i > 0) else 1
             idt = x
             out = F.relu(frozen_bn(F.conv2d(x, sd[p + "conv1.weight"]), sd, p + "bn1"))
+            i1 = _rec_conv(p + "conv1.weight", x, sd[p + "conv1.weight"], p + "bn1", sd, relu=True, y=out)
+            if prev_block is not None:
+                prev_block["next_c1"] = i1
+            o1 = out
             out = F.relu(frozen_bn(F.conv2d(out, sd[p + "conv2.weight"], None, stride=stride, padding=dil, dilation=dil), sd, p + "bn2"))
+            i2 = _rec_conv(p + "conv2.weight", o1, sd[p + "conv2.weight"], p + "bn2", sd, stride=stride, padding=dil, dilation=dil,
+                           relu=True, y=out)
+            o2 = out
             out = frozen_bn(F.conv2d(out, sd[p + "conv3.weight"]), sd, p + "bn3")
             if i == 0:
                 idt = frozen_bn(F.conv2d(x, sd[p + "downsample.0.weight"], None, stride=stride), sd, p + "downsample.1")
+                _rec_conv(p + "downsample.0.weight", x, sd[p + "downsample.0.weight"], p + "downsample.1", sd, stride=stride, y=idt)
             x = F.relu(out + idt)
+            i3 = _rec_conv(p + "conv3.weight", o2, sd[p + "conv3.weight"], p + "bn3", sd, res=idt, relu=True, y=x)
+            if F32_TRACE is not None:
+                prev_block = dict(kind="block", name=p, c2=i2, c3=i3, next_c1=None)
+                F32_TRACE.append(prev_block)
     return x
 
 
@@ -82,7 +122,31 @@ def _mha(sd, p, q, k, v, nheads):
     out, _ = F.multi_head_attention_forward(
         q, k, v, E, nheads, sd[p + "in_proj_weight"], sd[p + "in_proj_bias"], None, None, False, 0.0,
         sd[p + "out_proj.weight"], sd[p + "out_proj.bias"], training=False, key_padding_mask=None, need_weights=True)
+    if F32_TRACE is not None:      # the four projections as records (computed beside the call: its internals are not observable)
+        w, b = sd[p + "in_proj_weight"], sd[p + "in_proj_bias"]
+        proj = []
+        for j, t in enumerate((q, k, v)):
+            x = t.transpose(0, 1)                                          # [B, L, E]
+            y = F.linear(x, w[j * E:(j + 1) * E], b[j * E:(j + 1) * E])
+            _rec_lin(p + "in_proj." + "qkv"[j], x, w[j * E:(j + 1) * E], b[j * E:(j + 1) * E], y=y)
+            proj.append(y)
+        B_, Lq, Lk, hd = proj[0].shape[0], proj[0].shape[1], proj[1].shape[1], E // nheads
+        qh, kh, vh = (t.reshape(B_, -1, nheads, hd).transpose(1, 2) for t in proj)
+        att = torch.softmax(qh @ kh.transpose(-1, -2) / math.sqrt(hd), dim=-1) @ vh
+        att = att.transpose(1, 2).reshape(B_, Lq, E)
+        _rec_lin(p + "out_proj", att, sd[p + "out_proj.weight"], sd[p + "out_proj.bias"],
+                 y=F.linear(att, sd[p + "out_proj.weight"], sd[p + "out_proj.bias"]))
     return out
+
+
+def _ffn_rec(x, sd, p):
+    """the post-norm layers' feed-forward block, linear1 / linear2 recorded"""
+    h = F.relu(F.linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"]))
+    ff = F.linear(h, sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+    if F32_TRACE is not None:
+        _rec_lin(p + "linear1", x.transpose(0, 1), sd[p + "linear1.weight"], sd[p + "linear1.bias"], relu=True, y=h.transpose(0, 1))
+        _rec_lin(p + "linear2", h.transpose(0, 1), sd[p + "linear2.weight"], sd[p + "linear2.bias"], y=ff.transpose(0, 1))
+    return ff
 
 
 def _ln(x, sd, p):
@@ -141,8 +205,7 @@ def transformer(src, pos, query_embed, sd, nheads=8, enc_layers=6, dec_layers=6,
         p = f"{prefix}encoder.layers.{i}."
         q = k = x + pe
         x = _ln(x + _mha(sd, p + "self_attn.", q, k, x, nheads), sd, p + "norm1")
-        ff = F.linear(F.relu(F.linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"])),
-                      sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+        ff = _ffn_rec(x, sd, p)
         x = _ln(x + ff, sd, p + "norm2")
     memory = x
     tgt = torch.zeros_like(qe)
@@ -152,8 +215,7 @@ def transformer(src, pos, query_embed, sd, nheads=8, enc_layers=6, dec_layers=6,
         q = k = tgt + qe
         tgt = _ln(tgt + _mha(sd, p + "self_attn.", q, k, tgt, nheads), sd, p + "norm1")
         tgt = _ln(tgt + _mha(sd, p + "multihead_attn.", tgt + qe, memory + pe, memory, nheads), sd, p + "norm2")
-        ff = F.linear(F.relu(F.linear(tgt, sd[p + "linear1.weight"], sd[p + "linear1.bias"])),
-                      sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+        ff = _ffn_rec(tgt, sd, p)
         tgt = _ln(tgt + ff, sd, p + "norm3")
         inter.append(_ln(tgt, sd, prefix + "decoder.norm"))
     return torch.stack(inter).transpose(1, 2), memory
@@ -161,15 +223,23 @@ def transformer(src, pos, query_embed, sd, nheads=8, enc_layers=6, dec_layers=6,
 
 def _mlp(x, sd, p, n=3):
     for i in range(n):
+        x0 = x
         x = F.linear(x, sd[f"{p}.layers.{i}.weight"], sd[f"{p}.layers.{i}.bias"])
         if i < n - 1:
             x = F.relu(x)
+        _rec_lin(f"{p}.layers.{i}", x0, sd[f"{p}.layers.{i}.weight"], sd[f"{p}.layers.{i}.bias"], relu=i < n - 1, y=x)
     return x
+
+
+def _class_head(hs, sd):
+    y = F.linear(hs, sd["class_embed.weight"], sd["class_embed.bias"])
+    _rec_lin("class_embed", hs, sd["class_embed.weight"], sd["class_embed.bias"], y=y)
+    return y
 
 
 def heads(hs, sd):
     return {
-        "pred_logits": F.linear(hs, sd["class_embed.weight"], sd["class_embed.bias"]),
+        "pred_logits": _class_head(hs, sd),
         "pred_boxes": _mlp(hs, sd, "bbox_embed").sigmoid(),
         "pred_angle": _mlp(hs, sd, "angle_embed"),
         "pred_offset": _mlp(hs, sd, "offset_embed"),
@@ -187,6 +257,7 @@ def detr_forward(sd, img, blocks=(3, 4, 6, 3), nheads=8, enc_layers=6, dec_layer
     B, _, h, w = feat.shape
     pos = position_embedding_learned(sd, h, w, batch=B) if learned_pos else position_embedding(h, w, batch=B)
     src = F.conv2d(feat, sd["input_proj.weight"], sd["input_proj.bias"])
+    _rec_conv("input_proj.weight", feat, sd["input_proj.weight"], None, sd, bias=sd["input_proj.bias"], y=src)
     hs, memory = transformer(src, pos, sd["query_embed.weight"], sd, nheads, enc_layers, dec_layers, pre_norm=pre_norm)
     out = heads(hs[-1], sd)
     if return_taps:

@@ -323,12 +323,28 @@ def test_resnet101_configuration_vs_oracle():
     det.close()
 
 
+def _conv_paths(clear=False):
+    """tokens of the contraction launches since the last call (include/odam_detr.h odam_op_conv_paths)"""
+    from odam_amd import _lib
+    L = _lib.lib()
+    L.odam_op_conv_paths.restype = ctypes.c_longlong
+    if clear:
+        return L.odam_op_conv_paths(None, 0, 1)
+    buf = ctypes.create_string_buffer(1 << 17)
+    n = L.odam_op_conv_paths(buf, len(buf), 1)
+    toks = [t for t in buf.value.decode().split("\n") if t]
+    assert n == len(toks)
+    return toks
+
+
 @pytest.mark.parametrize("B,H,W,bb", [(3, 601, 795, "resnet50"), (2, 487, 1013, "resnet101")])
 def test_large_odd_sizes_vs_oracle(B, H, W, bb):
-    """Odd extents at sizes where the ring kernel, conv1-as-rows, the split attention and the fused layer1 / layer2
-    bottlenecks (incl. the chain into the next reduce) all apply: ragged last tiles in every one of them."""
+    """Odd extents at sizes where the ring kernel, conv1-as-rows, the split attention and the fused layer1 bottlenecks (incl. the
+    chain into the next reduce) all apply: ragged last tiles in every one of them.  Layer2 has too few rows here for its fused
+    launch by the default rule (3 x 76 x 100 = 22,800 rows, 90 tiles of the 192 needed): it runs fused in the nested cg.pin=1 pass
+    of test_conv_gemm_alternative_paths, and the tokens of the launches that ran are asserted in both."""
     import detr_oracle as O
-    from odam_amd import detector, weights
+    from odam_amd import _lib, detector, weights
     sd = weights.make_state_dict(backbone=bb, seed=0, scene=True)
     det = detector.Detector(backbone=bb, max_batch=B, device=DEV, n_streams=1)
     det.load_state_dict(sd)
@@ -336,7 +352,15 @@ def test_large_odd_sizes_vs_oracle(B, H, W, bb):
     img = torch.randn(B, 3, H, W)
     torch.set_num_threads(8)
     ref = O.detr_forward(sd, img, blocks=(3, 4, 23, 3) if bb == "resnet101" else (3, 4, 6, 3))
+    _conv_paths(clear=True)
     got = det(img.to(DEV))
+    torch.cuda.synchronize()
+    toks = _conv_paths()
+    cfg = _lib.config()
+    if cfg["cg.f32"] == 2 and cfg["cg.ring"] == 1 and cfg["cg.fuse"] == 2 and cfg["cg.mfma16"] == 3 and cfg["stem.rows"] == 1 and cfg["stem.pool"] == 1:
+        assert toks.count("f32.fused.m4.chain64") == 2 and toks.count("f32.fused.m4.chain128") == 1, toks[:12]
+        assert toks.count("f32.fused.m4.l2") == (4 if cfg["cg.pin"] else 0), toks[:24]
+        assert any(t.startswith("f32.ring.m4.256x") for t in toks) and any(".pool" in t for t in toks)
     for k in KEYS:
         assert (got[k].cpu() - ref[k]).abs().max().item() <= 2e-4 * max(1.0, ref[k].abs().max().item()), k
     assert torch.equal(got["pred_logits"].cpu().argmax(-1), ref["pred_logits"].argmax(-1))
@@ -781,7 +805,7 @@ def test_bf16_r101_full_size_vs_bf16_faithful_oracle(measured):
 
 
 @pytest.mark.parametrize("cfg", ["cg.ut=0", "cg.tiles=0", "cg.tiles=7", "cg.tiles=15", "cg.force=2", "cg.ring=2", "cg.ring=0", "cg.ring=2,cg.presplit=0", "cg.f32=0",
-                                 "att.x3=0,cg.fuse=1", "stem.rows=0,cg.fuse=0", "stem.pool=0", "cg.s1=0", "cg.fuse_bf16=0", "cg.fuse_bf16=1,att.bf16_mfma=0", "cg.mfma16=0", "cg.small_x3=0"])
+                                 "att.x3=0,cg.fuse=1", "stem.rows=0,cg.fuse=0", "stem.pool=0", "cg.s1=0", "cg.fuse_bf16=0", "cg.fuse_bf16=1,att.bf16_mfma=0", "cg.mfma16=0", "cg.small_x3=0", "cg.pin=1"])
 def test_conv_gemm_alternative_paths(cfg):
     """Every surviving switch of the library's config table (include/odam_config.h): the register-staged gather (what layers too
     large for 31-bit buffer offsets fall back to), the 4-wave tiles, the four-stage small-tile pipeline, the ring kernel
@@ -795,8 +819,10 @@ def test_conv_gemm_alternative_paths(cfg):
     if os.environ.get("ODAM_NESTED"):
         pytest.skip("already inside the nested run")
     sel = "conv_gemm_vs_torch or conv_gemm_bf16"
-    if cfg in ("cg.f32=0", "cg.mfma16=0", "cg.small_x3=0"):      # the reference-run goldens and the oracle comparisons must hold on the fp32 instruction as well
+    if cfg in ("cg.f32=0", "cg.mfma16=0", "cg.small_x3=0", "cg.pin=1"):      # the reference-run goldens and the oracle comparisons must hold on the fp32 instruction as well
         sel += " or reference_golden or vs_oracle or mixed_size"
+    if cfg == "cg.pin=1":      # what bench.py runs: every layer on the kernel a full device gets, the bf16 op tests too
+        sel += " or bf16_bottleneck"
     if "stem." in cfg or "cg.fuse=" in cfg:
         sel = "reference_golden or vs_oracle"
     if "att.x3" in cfg:

@@ -199,3 +199,51 @@ def test_select_nms_random_clusters_vs_oracle():
             assert np.array_equal(got["translates"], rows[want, 6:9]), (trial, nms_2d)
             n_kept += len(want)
     assert n_kept > 1000
+
+
+def _replay_f32(rec):
+    """a record of F32_TRACE recomputed with the forward's own operations"""
+    import torch.nn.functional as F
+    if rec["kind"] == "linear":
+        y = F.linear(rec["x"], rec["w"], rec["bias"])
+    elif rec["scale"] is None:
+        y = F.conv2d(rec["x"], rec["w"], rec["bias"], stride=rec["stride"], padding=rec["padding"], dilation=rec["dilation"])
+    else:
+        y = F.conv2d(rec["x"], rec["w"], None, stride=rec["stride"], padding=rec["padding"], dilation=rec["dilation"])
+        y = y * rec["scale"].reshape(1, -1, 1, 1) + rec["bias"].reshape(1, -1, 1, 1)
+    if rec["res"] is not None:
+        y = y + rec["res"]
+    return F.relu(y) if rec["relu"] else y
+
+
+@pytest.mark.parametrize("dilation", [False, True])
+def test_f32_trace(sd, dilation):
+    """oracle.F32_TRACE (the fp32 teacher-forcing records): tracing leaves every output bit-identical, every record reproduces its own
+    output bit for bit, and the counts are R50's -- 53 backbone convolutions + input_proj, 6 x 6 encoder and 6 x 10 decoder linears
+    (four attention projections each, two feed-forward) + 16 head linears -- with 16 block records that point at their layers"""
+    torch.manual_seed(5)
+    img = torch.randn(1, 3, 96, 128)
+    plain = O.detr_forward(sd, img, dilation=dilation)
+    O.F32_TRACE = []
+    try:
+        traced = O.detr_forward(sd, img, dilation=dilation)
+        trace = O.F32_TRACE
+    finally:
+        O.F32_TRACE = None
+    for k in KEYS:
+        assert torch.equal(plain[k], traced[k]), k
+    convs = [r for r in trace if r["kind"] == "conv"]
+    lins = [r for r in trace if r["kind"] == "linear"]
+    blocks = [r for r in trace if r["kind"] == "block"]
+    assert sum(r["name"].startswith("backbone.") for r in convs) == 53 and len(convs) == 54
+    assert len(lins) == 6 * 6 + 6 * 10 + 16
+    assert len(blocks) == 16 and sum(b["next_c1"] is None for b in blocks) == 1
+    assert sum(r["dilation"] == 2 for r in convs) == (2 if dilation else 0)
+    for r in convs + lins:
+        assert torch.equal(_replay_f32(r), r["y"]), r["name"]
+    for b in blocks:
+        c2, c3 = trace[b["c2"]], trace[b["c3"]]
+        assert c2["name"] == b["name"] + "conv2.weight" and c3["name"] == b["name"] + "conv3.weight"
+        assert c3["x"] is c2["y"] and c3["res"] is not None
+        if b["next_c1"] is not None:
+            assert trace[b["next_c1"]]["x"] is c3["y"] and trace[b["next_c1"]]["name"].endswith("conv1.weight")
