@@ -37,7 +37,10 @@ typedef struct {
     int max_batch;         /* frames per forward call */
     int img_h, img_w;      /* network input size, e.g. 800 x 1066 for a 640x480 frame (transforms.py:78-96) */
     int dtype;             /* 0: fp32 everywhere (parity mode).  1: bf16 weights + activations in memory, bf16 MFMA
-                              with fp32 accumulation, fp32 softmax / LayerNorm / head outputs (BASELINE config 4) */
+                              with fp32 accumulation, fp32 softmax / LayerNorm / head outputs (BASELINE config 4).
+                              2: mxfp8 -- every convolution of the ResNet body on MXFP8 operands (below) with fp32 accumulation
+                              on v_mfma_scale_f32_32x32x64_f8f6f4; the stem, input_proj, the transformer and the heads exactly as
+                              in 1.  Refused together with `dilation` */
     int pre_norm;          /* 0: post-norm layers (the shipped configuration).  1: `normalize_before` -- every encoder / decoder
                               sub-block normalises its input and adds its output to the stream, the encoder ends in its own
                               LayerNorm "transformer.encoder.norm.*" (src/models/transformer.py:169-188, 240-262, 26-28) */
@@ -120,6 +123,26 @@ int odam_detr_profile_enable(odam_detr* m, int on);
 int odam_detr_profile_read(odam_detr* m, int* n_launches, double* total_ms, double* total_flops);
 int odam_detr_profile_read_attention(odam_detr* m, int* n_launches, double* total_ms, double* total_flops);
 
+/*
+ * MXFP8 (dtype 2): OCP MX v1.0 with these choices fixed --
+ *   elements  e4m3fn (the OCP encoding, not MI300's fnuz), converted round-to-nearest-even with subnormals kept;
+ *   scales    one E8M0 byte (2^(s - 127)) per block of 32 values: 32 consecutive channels of one NHWC pixel for activations,
+ *             32 consecutive k of one output channel for filters (k = (ky KW + kx) Cin + ci).  A tensor [rows][C] is elements
+ *             [rows][C] + scales [rows][C / 32]: the scale of element i is scale[i / 32];
+ *   rule      e = the smallest integer with amax <= 448 * 2^e, clamped to [-127, 127]; an all-zero block gets -127.  Elements are
+ *             x * 2^-e (exact) rounded to e4m3fn, so none saturates (the OCP default floor(log2 amax) - 8 would clip up to one
+ *             binade of the block maximum).  A block holding a NaN or an Inf is outside the contract: its scale byte is 0xFF
+ *             (the E8M0 NaN), so it dequantizes -- and multiplies -- to NaN; its element bytes are not specified.
+ * Storage in the mxfp8 forward: a tensor a convolution reads is MXFP8; the downsample output (read only as a residual) is bf16;
+ * block outputs are written in both forms; the residual add and the FrozenBN scale / bias run in fp32 in the epilogue.  The
+ * pooled stem is bf16 and quantized once; layer4's last output is bf16 only (input_proj reads it, odam_detr_debug_read returns it).
+ */
+
+/* per-stage totals of the contraction launches of the most recent profiled forward (odam_detr_profile_enable): n >= 6 entries,
+ * [0] stem, [1..4] layer1 .. layer4, [5] input_proj, transformer projections / FFN and heads.  A fused bf16 launch that also
+ * computes the next stage's first reduce counts in the stage it starts in. */
+int odam_detr_profile_read_stages(odam_detr* m, int n, int* launches, double* ms, double* flops);
+
 /* ---- single-operator entry points (the same kernels the forward uses; for parity tests and reuse) ---- */
 /* NHWC convolution / linear:  x [dev][B,H,W,Cin] (Cin power of two >= 4), w_packed [dev][Cout][Kpad], zero padded
  * to a multiple of the k-tile (32 fp32 / 64 bf16), scale/bias/residual nullable, y [dev][B,Ho,Wo,Cout].
@@ -164,6 +187,7 @@ int odam_op_bottleneck_f32(const float* x, const float* w2, const float* s2, con
  *                 bf16.ring.<rows>x<cols>[.pool]           .pool: conv1 with the max-pool on its tile
  *   bottleneck    f32.fused.m<3|4>.<l1|chain64|chain128|l2>   l1: 64-channel 3x3 + expand, chain64 / chain128: + the next reduce,
  *                 bf16.fused.p<P>[.chain<PN>]                 l2: 128-channel 3x3 + expand
+ *   mxfp8         mx8.<BN>x<BM>.w<waves>                      every MXFP8 convolution (odam_op_conv2d_nhwc_mxfp8, the mxfp8 body)
  * The fp32 tokens, all of them (tests/test_conv_f32_gpu.py covers each):
  *   FP32-TOKENS-BEGIN
  *   f32.small.128x64.w4 f32.small.128x64.w4.ut f32.small.128x64.w4.ut.x3 f32.small.128x64.w8 f32.small.128x64.w8.ut
@@ -207,6 +231,18 @@ int odam_op_attention_ex(const void* Q, int ldq, const void* K, int ldk, const v
  * dtype 0 fp32 / 1 bf16, gamma / beta / pos fp32; y = LN(x + r) * gamma + beta, y_pos[row] = y[row] + pos[row % L] */
 int odam_op_add_layernorm_ex(const void* x, const void* r, const float* gamma, const float* beta, void* y,
                              const float* pos, int L, void* y_pos, int M, int dtype, void* stream);
+/* MXFP8 tensors (format above).  n elements, n % 32 == 0: x [dev] fp32 (src_dtype 0) or bf16 (1) -> q [dev][n] + s [dev][n / 32] */
+int odam_op_quantize_mxfp8(const void* x, int src_dtype, long long n, void* q, void* s, void* stream);
+int odam_op_dequantize_mxfp8(const void* q, const void* s, long long n, float* y, void* stream);
+/* MXFP8 convolution (the mxfp8 forward's kernel, one launch): x / xs [dev] MXFP8 NHWC input [B,H,W,Cin] (Cin % 64 == 0),
+ * w_packed / ws [dev] MXFP8 filters [Cout][Kpad] (Cout % 32 == 0, Kpad = KH KW Cin, k_order 0 only; dil 1 only), scale / bias fp32
+ * nullable, residual [dev] bf16 [M][Cout] nullable; epilogue act(acc * scale + bias + residual) in fp32, then per 32-channel block
+ * of a pixel the outputs y / ys MXFP8 (nullable together), y_bf16 (nullable) and y_f32 (nullable: the values before quantization).
+ * Notes token mx8.128x128.w4. */
+int odam_op_conv2d_nhwc_mxfp8(const void* x, const void* xs, const void* w_packed, const void* ws, const float* scale,
+                              const float* bias, const void* residual, void* y, void* ys, void* y_bf16, float* y_f32,
+                              int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                              int Kpad, int relu, int k_order, void* stream);
 int odam_op_maxpool3x3s2_nhwc(const float* x, float* y, int B, int H, int W, int C, void* stream);
 
 #ifdef __cplusplus

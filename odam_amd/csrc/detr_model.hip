@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/odam_detr.h"
+#include "cg_mx8.h"
 #include "conv_gemm.h"
 #include "detr_kernels.h"
 #include "odam_config.h"
@@ -38,6 +39,8 @@ struct Conv {          // packed convolution / linear layer on device
     float* bias = nullptr;   // [Cout] or null
     int Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad = 0, Kpad = 0, dil = 1;
     int k_order = 0;         // conv_gemm.h: 1 = channel-chunk-major K (multi-tap filters with Cin % k-tile == 0)
+    unsigned char* wq = nullptr;    // mxfp8 body layers: MXFP8 filters [Cout][Kpad] (k = tap * Cin + ci) and their scales
+    unsigned char* wqs = nullptr;   //    [Cout][Kpad / 32] (cg_mx8.h); w is then null
 };
 
 struct Bottleneck {     // one residual block: Bottleneck c1 1x1, c2 3x3 (stride), c3 1x1 + residual; BasicBlock (odam_detr::basic)
@@ -91,7 +94,13 @@ struct odam_detr {
          *dtmp = nullptr, *dffn = nullptr, *hs = nullptr, *h1 = nullptr, *h2 = nullptr;
     const char* layer4 = nullptr;  // where the last forward left the layer4 map (NHWC)
     int es = 4;                    // bytes per activation / weight element
-    int dt = 0;                    // 0 fp32, 1 bf16
+    int dt = 0;                    // 0 fp32, 1 bf16 (also the mxfp8 mode's: everything outside the ResNet body runs as in bf16)
+    bool mx = false;               // cfg.dtype 2: the body's convolutions on MXFP8 operands (cg_mx8.h)
+    // mxfp8 workspace: block inputs / outputs (elements + scales; their bf16 forms live in bufA / bufB), the 1x1 reduce
+    // and 3x3 outputs; the downsample output (a residual only) is bf16 in dsb
+    unsigned char *qa = nullptr, *qas = nullptr, *qb = nullptr, *qbs = nullptr, *qt1 = nullptr, *qt1s = nullptr, *qt2 = nullptr,
+                  *qt2s = nullptr;
+    size_t stage_ev[6] = {};       // ev_used where the stem, layer1 .. layer4 and the rest (input_proj .. heads) began
 
     // optional per-launch timing of the contraction kernel (bench.py roofline): event pairs around every
     // conv_gemm launch of a forward, read back by odam_detr_profile_read
@@ -162,6 +171,12 @@ const HostTensor* find(odam_detr* m, const std::string& name) {
         return 1;                                                                          \
     }
 
+#define RC(call)                 \
+    do {                         \
+        int rc_ = (call);        \
+        if (rc_) return rc_;     \
+    } while (0)
+
 // [Cout, Cin, KH, KW] (PyTorch) -> [Cout][Kpad], k = (ky*KW + kx)*CinP + ci, CinP = Cin rounded up to 4
 int pack_conv(odam_detr* m, Conv& c, const HostTensor& w, int stride, int pad, int dil = 1) {
     const int Cout = (int)w.shape[0], Cin = (int)w.shape[1];
@@ -185,6 +200,30 @@ int pack_conv(odam_detr* m, Conv& c, const HostTensor& w, int stride, int pad, i
     c.Cin = CinP; c.Cout = Cout; c.KH = KH; c.KW = KW; c.stride = stride; c.pad = pad; c.Kpad = Kpad; c.dil = dil;
     if (int rc = m->upload_w3(&c.w3, p, Cout, Kpad)) return rc;
     return m->upload_w(&c.w, p);
+}
+
+int pack_conv1(odam_detr* m, Conv& c, const HostTensor& w, int stride, int pad) { return pack_conv(m, c, w, stride, pad); }
+
+// mxfp8 body layer: [Cout, Cin, KH, KW] -> MXFP8 [Cout][Kpad = KH KW Cin], k = (ky KW + kx) Cin + ci, scales per 32 k (cg_mx8.h)
+int pack_conv_mx(odam_detr* m, Conv& c, const HostTensor& w, int stride, int pad) {
+    const int Cout = (int)w.shape[0], Cin = (int)w.shape[1];
+    const int KH = w.shape.size() > 2 ? (int)w.shape[2] : 1, KW = w.shape.size() > 3 ? (int)w.shape[3] : 1;
+    if (Cin % 64 || Cout % 32) return odam_fail(1, "odam_detr_finalize: mxfp8 body layers need Cin % 64 == 0 and Cout % 32 == 0");
+    const int Kpad = KH * KW * Cin;
+    std::vector<float> p((size_t)Cout * Kpad);
+    for (int o = 0; o < Cout; o++)
+        for (int ci = 0; ci < Cin; ci++)
+            for (int ky = 0; ky < KH; ky++)
+                for (int kx = 0; kx < KW; kx++)
+                    p[(size_t)o * Kpad + (ky * KW + kx) * Cin + ci] = w.data[(((size_t)o * Cin + ci) * KH + ky) * KW + kx];
+    std::vector<unsigned char> q(p.size()), qs(p.size() / 32);
+    odam_mx::quantize_host(p.data(), p.size(), q.data(), qs.data());
+    c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.stride = stride; c.pad = pad; c.Kpad = Kpad; c.dil = 1; c.k_order = 0;
+    RC(m->dev_alloc(&c.wq, q.size()));
+    RC(m->dev_alloc(&c.wqs, qs.size()));
+    ODAM_HIP(hipMemcpy(c.wq, q.data(), q.size(), hipMemcpyHostToDevice));
+    ODAM_HIP(hipMemcpy(c.wqs, qs.data(), qs.size(), hipMemcpyHostToDevice));
+    return 0;
 }
 
 // rows [r0, r1) of a [N, K] Linear weight (+ bias) as a 1x1 layer
@@ -371,6 +410,31 @@ int lin_t(odam_detr* m, const Conv& c, const void* x, int M, const void* res, bo
           int out_f32 = 0) {
     return conv_t(m, c, x, 1, 1, M, res, relu, y, st, out_f32);
 }
+// an mxfp8 body layer: x / xs MXFP8 input, res bf16 (nullable); outputs y / ys MXFP8 and / or yb bf16 (nullable); timed as conv_t
+int mx_t(odam_detr* m, const Conv& c, const unsigned char* x, const unsigned char* xs, int B, int H, int W, const void* res, bool relu,
+         unsigned char* y, unsigned char* ys, void* yb, hipStream_t st) {
+    odam_mx::ConvArgs a{};
+    a.x = x; a.xs = xs; a.w = c.wq; a.ws = c.wqs; a.scale = c.scale; a.bias = c.bias; a.res = (const unsigned short*)res;
+    a.y = y; a.ys = ys; a.yb = (unsigned short*)yb; a.yf = nullptr;
+    a.B = B; a.H = H; a.W = W; a.Cin = c.Cin; a.Ho = conv_out(H, c.KH, c.stride, c.pad); a.Wo = conv_out(W, c.KW, c.stride, c.pad);
+    a.Cout = c.Cout; a.KH = c.KH; a.KW = c.KW; a.stride = c.stride; a.pad = c.pad; a.Kpad = c.Kpad; a.relu = relu ? 1 : 0;
+    a.M = B * a.Ho * a.Wo;
+    if (!m->profile) return odam_mx::launch_conv(a, st);
+    if (m->ev_used + 2 > m->ev.size()) {
+        for (int k = 0; k < 2; k++) {
+            hipEvent_t e;
+            ODAM_HIP(hipEventCreate(&e));
+            m->ev.push_back(e);
+        }
+        m->ev_flops.resize(m->ev.size() / 2);
+    }
+    m->ev_flops[m->ev_used / 2] = 2.0 * a.M * (double)c.Cout * c.Kpad;
+    ODAM_HIP(hipEventRecord(m->ev[m->ev_used], st));
+    int rc = odam_mx::launch_conv(a, st);
+    ODAM_HIP(hipEventRecord(m->ev[m->ev_used + 1], st));
+    m->ev_used += 2;
+    return rc;
+}
 int att_t(odam_detr* m, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
           int B, int H, int Lq, int Lk, hipStream_t st, const unsigned char* key_mask = nullptr) {
     if (!m->profile) return odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, m->dt, st, key_mask);
@@ -390,12 +454,6 @@ int att_t(odam_detr* m, const void* Q, int ldq, const void* K, int ldk, const vo
     return rc;
 }
 
-#define RC(call)                 \
-    do {                         \
-        int rc_ = (call);        \
-        if (rc_) return rc_;     \
-    } while (0)
-
 }  // namespace
 
 extern "C" int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out) {
@@ -403,7 +461,9 @@ extern "C" int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out) {
     if (cfg->hidden_dim != 256 || cfg->nheads != 8)
         return odam_fail(3, "odam_detr_create: kernels are built for hidden_dim 256, 8 heads (head dim 32)");
     if (cfg->max_batch < 1 || cfg->img_h < 32 || cfg->img_w < 32) return odam_fail(1, "odam_detr_create: bad sizes");
-    if (cfg->dtype != 0 && cfg->dtype != 1) return odam_fail(1, "odam_detr_create: dtype must be 0 (fp32) or 1 (bf16)");
+    if (cfg->dtype < 0 || cfg->dtype > 2) return odam_fail(1, "odam_detr_create: dtype must be 0 (fp32), 1 (bf16) or 2 (mxfp8)");
+    if (cfg->dtype == 2 && cfg->dilation)
+        return odam_fail(3, "odam_detr_create: dilation (DC5) is not supported in the mxfp8 mode (dtype 2)");
     if (cfg->basic_block != 0 && cfg->basic_block != 1) return odam_fail(1, "odam_detr_create: basic_block must be 0 (Bottleneck) or 1 (BasicBlock)");
     if (cfg->basic_block && cfg->dilation)      // torchvision BasicBlock: "Dilation > 1 not supported in BasicBlock"
         return odam_fail(3, "odam_detr_create: dilation (DC5) is not supported with BasicBlock backbones (resnet18 / resnet34)");
@@ -412,7 +472,8 @@ extern "C" int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out) {
     odam_detr* m = new odam_detr();
     m->cfg = *cfg;
     m->basic = cfg->basic_block != 0;
-    m->dt = cfg->dtype;
+    m->mx = cfg->dtype == 2;
+    m->dt = cfg->dtype ? 1 : 0;
     m->es = cfg->dtype ? 2 : 4;
     m->H1 = conv_out(cfg->img_h, 7, 2, 3); m->W1 = conv_out(cfg->img_w, 7, 2, 3);
     m->H2 = conv_out(m->H1, 3, 2, 1); m->W2 = conv_out(m->W1, 3, 2, 1);
@@ -492,12 +553,12 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
                 NEED(w1, p + "conv1.weight"); NEED(w2, p + "conv2.weight");
                 RC(check_shape(*w1, planes, inplanes, 3, p + "conv1.weight"));
                 RC(check_shape(*w2, planes, planes, 3, p + "conv2.weight"));
-                RC(pack_conv(m, b.c1, *w1, stride, 1)); RC(fold_bn(m, b.c1, p + "bn1"));
-                RC(pack_conv(m, b.c2, *w2, 1, 1)); RC(fold_bn(m, b.c2, p + "bn2"));
+                RC((m->mx ? pack_conv_mx : pack_conv1)(m, b.c1, *w1, stride, 1)); RC(fold_bn(m, b.c1, p + "bn1"));
+                RC((m->mx ? pack_conv_mx : pack_conv1)(m, b.c2, *w2, 1, 1)); RC(fold_bn(m, b.c2, p + "bn2"));
                 if (ds) {
                     NEED(wd, p + "downsample.0.weight");
                     RC(check_shape(*wd, planes, inplanes, 1, p + "downsample.0.weight"));
-                    RC(pack_conv(m, b.ds, *wd, stride, 0)); RC(fold_bn(m, b.ds, p + "downsample.1"));
+                    RC((m->mx ? pack_conv_mx : pack_conv1)(m, b.ds, *wd, stride, 0)); RC(fold_bn(m, b.ds, p + "downsample.1"));
                     b.has_ds = true;
                 }
                 m->blocks.push_back(b);
@@ -513,12 +574,17 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
             const int dil = (dc5 && i > 0) ? 2 : 1;
             Bottleneck b;
             NEED(w1, p + "conv1.weight"); NEED(w2, p + "conv2.weight"); NEED(w3, p + "conv3.weight");
-            RC(pack_conv(m, b.c1, *w1, 1, 0)); RC(fold_bn(m, b.c1, p + "bn1"));
-            RC(pack_conv(m, b.c2, *w2, stride, dil, dil)); RC(fold_bn(m, b.c2, p + "bn2"));   // v1.5: stride on the 3x3
-            RC(pack_conv(m, b.c3, *w3, 1, 0)); RC(fold_bn(m, b.c3, p + "bn3"));
+            if (m->mx) {        // no dilation here (refused at create)
+                RC(pack_conv_mx(m, b.c1, *w1, 1, 0)); RC(pack_conv_mx(m, b.c2, *w2, stride, 1)); RC(pack_conv_mx(m, b.c3, *w3, 1, 0));
+            } else {
+                RC(pack_conv(m, b.c1, *w1, 1, 0));
+                RC(pack_conv(m, b.c2, *w2, stride, dil, dil));    // v1.5: stride on the 3x3
+                RC(pack_conv(m, b.c3, *w3, 1, 0));
+            }
+            RC(fold_bn(m, b.c1, p + "bn1")); RC(fold_bn(m, b.c2, p + "bn2")); RC(fold_bn(m, b.c3, p + "bn3"));
             if (i == 0) {
                 NEED(wd, p + "downsample.0.weight");
-                RC(pack_conv(m, b.ds, *wd, stride, 0)); RC(fold_bn(m, b.ds, p + "downsample.1"));
+                RC((m->mx ? pack_conv_mx : pack_conv1)(m, b.ds, *wd, stride, 0)); RC(fold_bn(m, b.ds, p + "downsample.1"));
                 b.has_ds = true;
             }
             m->blocks.push_back(b);
@@ -618,6 +684,12 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
     RC(m->dev_alloc(&m->stem_out, B * m->H1 * m->W1 * 64 * es));
     RC(m->dev_alloc(&m->bufA, big)); RC(m->dev_alloc(&m->bufB, big)); RC(m->dev_alloc(&m->dsb, big));
     RC(m->dev_alloc(&m->t1, tsz)); RC(m->dev_alloc(&m->t2, tsz));
+    if (m->mx) {        // element counts: big / es (block inputs / outputs), tsz / es (reduce / 3x3 outputs); one scale per 32
+        RC(m->dev_alloc(&m->qa, big / es)); RC(m->dev_alloc(&m->qb, big / es));
+        RC(m->dev_alloc(&m->qas, big / es / 32)); RC(m->dev_alloc(&m->qbs, big / es / 32));
+        RC(m->dev_alloc(&m->qt1, tsz / es)); RC(m->dev_alloc(&m->qt2, tsz / es));
+        RC(m->dev_alloc(&m->qt1s, tsz / es / 32)); RC(m->dev_alloc(&m->qt2s, tsz / es / 32));
+    }
     const size_t M = B * m->L, Mq = B * c.num_queries, F = c.dim_feedforward;
     RC(m->dev_alloc(&m->src, M * E * es)); RC(m->dev_alloc(&m->srcpos, M * E * es)); RC(m->dev_alloc(&m->qk, M * 2 * E * es));
     RC(m->dev_alloc(&m->v, M * E * es)); RC(m->dev_alloc(&m->att, M * E * es)); RC(m->dev_alloc(&m->tmp, M * E * es));
@@ -677,7 +749,45 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
     char* tin = m->t1;          // where this block's 1x1 reduce output lives (the 3x3's input)
     char* tout = m->t2;         // the other small buffer: the 3x3's output, or -- chained -- the NEXT block's reduce output
     bool have_c1 = false;       // the previous block's launch already computed this block's reduce
-    for (size_t i = 0; m->basic && i < m->blocks.size(); i++) {
+    // per-stage profile: where each ResNet stage's launches begin (odam_detr_profile_read_stages)
+    std::fill(m->stage_ev, m->stage_ev + 6, m->ev_used);
+    m->stage_ev[0] = 0;
+    auto mark = [&](size_t i) {
+        for (int l = 0, first = 0; l < 4; first += c.resnet_blocks[l], l++)
+            if ((int)i == first) m->stage_ev[l + 1] = m->ev_used;
+    };
+    if (m->mx) {
+        // mxfp8: every body convolution on MXFP8 operands, one launch per layer (cg_mx8.hip).  Block inputs / outputs are
+        // written in both forms -- MXFP8 (cq / cs, read by conv1 and the downsample) and bf16 (cur, read as the residual); the
+        // downsample output is bf16 only (a residual); layer4's last output only bf16 (input_proj reads it)
+        unsigned char *cq = m->qa, *cs = m->qas, *nq = m->qb, *ns = m->qbs;
+        RC(odam_mx::launch_quantize(cur, 1, (size_t)B * H * W * 64, cq, cs, st));      // the pooled stem, bf16 in bufA
+        for (size_t i = 0; i < m->blocks.size(); i++) {
+            mark(i);
+            const Bottleneck& b = m->blocks[i];
+            const int s = m->block_stride[i];
+            const int Ho = conv_out(H, 3, s, 1), Wo = conv_out(W, 3, s, 1);
+            const bool last = i + 1 == m->blocks.size();
+            unsigned char* oq = last ? nullptr : nq;
+            unsigned char* os = last ? nullptr : ns;
+            RC(mx_t(m, b.c1, cq, cs, B, H, W, nullptr, true, m->qt1, m->qt1s, nullptr, st));
+            const char* res = cur;
+            if (b.has_ds) {
+                RC(mx_t(m, b.ds, cq, cs, B, H, W, nullptr, false, nullptr, nullptr, m->dsb, st));
+                res = m->dsb;
+            }
+            if (m->basic) {
+                RC(mx_t(m, b.c2, m->qt1, m->qt1s, B, Ho, Wo, res, true, oq, os, nxt, st));
+            } else {
+                RC(mx_t(m, b.c2, m->qt1, m->qt1s, B, H, W, nullptr, true, m->qt2, m->qt2s, nullptr, st));
+                RC(mx_t(m, b.c3, m->qt2, m->qt2s, B, Ho, Wo, res, true, oq, os, nxt, st));
+            }
+            std::swap(cur, nxt); std::swap(cq, nq); std::swap(cs, ns);
+            H = Ho; W = Wo;
+        }
+    }
+    for (size_t i = 0; !m->mx && m->basic && i < m->blocks.size(); i++) {
+        mark(i);
         // BasicBlock: conv1 (3x3 / stride) + bn1 + ReLU -> t1; conv2 (3x3) + bn2 + identity or downsample + ReLU in conv2's epilogue
         const Bottleneck& b = m->blocks[i];
         const int s = m->block_stride[i];
@@ -692,7 +802,8 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
         char* t = cur; cur = nxt; nxt = t;
         H = Ho; W = Wo;
     }
-    for (size_t i = 0; !m->basic && i < m->blocks.size(); i++) {
+    for (size_t i = 0; !m->mx && !m->basic && i < m->blocks.size(); i++) {
+        mark(i);
         const Bottleneck& b = m->blocks[i];
         const int s = m->block_stride[i];
         const int Ho = conv_out(H, 3, s, 1), Wo = conv_out(W, 3, s, 1);
@@ -720,6 +831,7 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
         H = Ho; W = Wo;
     }
     m->layer4 = cur;
+    m->stage_ev[5] = m->ev_used;
     const int L = m->L, M = B * L, Mq = B * Q;
 
     // ---- input_proj + encoder (detr.py:70, transformer.py:154-167) -----------------------------
@@ -904,6 +1016,35 @@ extern "C" int odam_op_conv2d_nhwc_bf16(const void* x, const void* w_packed, con
     return run_conv(c, x, B, H, W, residual, relu != 0, y, 0, (hipStream_t)stream, 1, out_f32);
 }
 
+// ---- MXFP8 (cg_mx8.h) ----
+extern "C" int odam_op_quantize_mxfp8(const void* x, int src_dtype, long long n, void* q, void* s, void* stream) {
+    if (!x || !q || !s || n < 0) return odam_fail(1, "odam_op_quantize_mxfp8: null pointer or negative count");
+    if (src_dtype != 0 && src_dtype != 1) return odam_fail(1, "odam_op_quantize_mxfp8: src_dtype must be 0 (fp32) or 1 (bf16)");
+    return odam_mx::launch_quantize(x, src_dtype, (size_t)n, (unsigned char*)q, (unsigned char*)s, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_dequantize_mxfp8(const void* q, const void* s, long long n, float* y, void* stream) {
+    if (!q || !s || !y || n < 0) return odam_fail(1, "odam_op_dequantize_mxfp8: null pointer or negative count");
+    return odam_mx::launch_dequantize((const unsigned char*)q, (const unsigned char*)s, (size_t)n, y, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_conv2d_nhwc_mxfp8(const void* x, const void* xs, const void* w_packed, const void* ws, const float* scale,
+                                         const float* bias, const void* residual, void* y, void* ys, void* y_bf16, float* y_f32,
+                                         int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                                         int Kpad, int relu, int k_order, void* stream) {
+    if (dil != 1) return odam_fail(1, "odam_op_conv2d_nhwc_mxfp8: dilation must be 1");
+    if (k_order != 0) return odam_fail(1, "odam_op_conv2d_nhwc_mxfp8: k_order must be 0 (tap-major)");
+    if (B < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0) return odam_fail(1, "odam_op_conv2d_nhwc_mxfp8: bad shape");
+    odam_mx::ConvArgs a{};
+    a.x = (const unsigned char*)x; a.xs = (const unsigned char*)xs; a.w = (const unsigned char*)w_packed; a.ws = (const unsigned char*)ws;
+    a.scale = scale; a.bias = bias; a.res = (const unsigned short*)residual;
+    a.y = (unsigned char*)y; a.ys = (unsigned char*)ys; a.yb = (unsigned short*)y_bf16; a.yf = y_f32;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = conv_out(H, KH, stride, pad); a.Wo = conv_out(W, KW, stride, pad);
+    a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.Kpad = Kpad; a.relu = relu ? 1 : 0;
+    a.M = B * a.Ho * a.Wo;
+    return odam_mx::launch_conv(a, (hipStream_t)stream);
+}
+
 // A whole bf16 bottleneck tail as ONE launch (conv_gemm.hip fused_bf16): 3x3 (P -> P channels, stride 1 or 2, pad 1; filters
 // packed k_order 1) + scale / bias / ReLU, 1x1 expand to 4 P channels + scale / bias + residual + ReLU -> y, and optionally the
 // next block's 1x1 reduce (4 P -> PN channels, scale / bias / ReLU) of y -> y_next.  Returns 4 where the fused kernel does
@@ -1057,6 +1198,22 @@ extern "C" int odam_detr_profile_read(odam_detr* m, int* n_launches, double* tot
     *n_launches = (int)(m->ev_used / 2);
     *total_ms = ms;
     *total_flops = fl;
+    return 0;
+}
+
+extern "C" int odam_detr_profile_read_stages(odam_detr* m, int n, int* launches, double* ms, double* flops) {
+    if (!m || n < 6 || !launches || !ms || !flops) return odam_fail(1, "odam_detr_profile_read_stages: null argument or n < 6");
+    for (int s = 0; s < 6; s++) { launches[s] = 0; ms[s] = 0.0; flops[s] = 0.0; }
+    for (size_t i = 0; i + 1 < m->ev_used; i += 2) {
+        int s = 0;
+        while (s < 5 && m->stage_ev[s + 1] <= i) s++;
+        ODAM_HIP(hipEventSynchronize(m->ev[i + 1]));
+        float t = 0.0f;
+        ODAM_HIP(hipEventElapsedTime(&t, m->ev[i], m->ev[i + 1]));
+        launches[s]++;
+        ms[s] += t;
+        flops[s] += m->ev_flops[i / 2];
+    }
     return 0;
 }
 

@@ -90,8 +90,10 @@ class Detector:
         self.pre_norm = bool(pre_norm)
         self.dilation = bool(dilation)
         self.resize = (800, 1333)   # get_transforms(): shortest side, longest-side cap (transforms.py:281-290)
-        if dtype not in ("fp32", "bf16"):
-            raise ValueError("dtype must be 'fp32' (parity mode) or 'bf16' (BASELINE config 4)")
+        if dtype not in ("fp32", "bf16", "mxfp8"):
+            raise ValueError("dtype must be 'fp32' (parity mode), 'bf16' (BASELINE config 4) or 'mxfp8' (MXFP8 ResNet body)")
+        if dtype == "mxfp8" and dilation:
+            raise ValueError("dtype='mxfp8': dilation (DC5) is not supported in the mxfp8 mode")
         self.dtype = dtype
         self.arch = dict(backbone=backbone, hidden_dim=hidden_dim, nheads=nheads, dim_feedforward=dim_feedforward,
                          enc_layers=enc_layers, dec_layers=dec_layers, num_queries=num_queries,
@@ -152,7 +154,7 @@ class Detector:
                   "angle_bins"):
             setattr(cfg, k, a[k])
         cfg.max_batch, cfg.img_h, cfg.img_w = self.max_batch, H, W
-        cfg.dtype = 1 if self.dtype == "bf16" else 0
+        cfg.dtype = {"fp32": 0, "bf16": 1, "mxfp8": 2}[self.dtype]
         cfg.pre_norm = 1 if self.pre_norm else 0
         cfg.dilation = 1 if self.dilation else 0
         cfg.basic_block = 1 if self.basic_block else 0
@@ -469,6 +471,15 @@ class Detector:
         _lib.check(_lib.lib().odam_detr_profile_read_attention(self._handle(H, W), ctypes.byref(n), ctypes.byref(ms),
                                                                ctypes.byref(fl)), "profile_read_attention")
         return n.value, ms.value, fl.value
+
+    def profile_read_stages(self, H, W):
+        """per-stage totals of the last profiled forward: {stage: (launches, ms, flops)} for stem, layer1 .. layer4 and rest
+        (input_proj, the transformer's projections / FFN and the heads; attention is profile_read_attention)"""
+        n = (ctypes.c_int * 6)()
+        ms, fl = (ctypes.c_double * 6)(), (ctypes.c_double * 6)()
+        _lib.check(_lib.lib().odam_detr_profile_read_stages(self._handle(H, W), ctypes.c_int(6), n, ms, fl), "profile_read_stages")
+        names = ("stem", "layer1", "layer2", "layer3", "layer4", "rest")
+        return {k: (n[i], ms[i], fl[i]) for i, k in enumerate(names)}
 
     def postprocess(self, out, img_size, threshold, intr_mat, nms_2d=True):
         rows = self.postprocess_rows(out, img_size, intr_mat)
