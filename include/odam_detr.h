@@ -26,8 +26,9 @@ typedef struct odam_detr odam_detr;
 typedef struct {
     int resnet_blocks[4];  /* blocks per stage (backbone.py:90): Bottleneck {3,4,6,3} = resnet50, {3,4,23,3} = resnet101,
                               {3,8,36,3} = resnet152; BasicBlock (basic_block = 1) {2,2,2,2} = resnet18, {3,4,6,3} = resnet34 */
-    int hidden_dim;        /* 256  (configs/detr_scan_net.yaml) */
-    int nheads;            /* 8    head dim must be 32 */
+    int hidden_dim;        /* 256  (configs/detr_scan_net.yaml); a multiple of 64 in 128 .. 1024 */
+    int nheads;            /* 8    hidden_dim % nheads == 0 and head dim hidden_dim / nheads 32 or 64 (else
+                              odam_detr_create returns 3) */
     int dim_feedforward;   /* 2048 */
     int enc_layers;        /* 6 */
     int dec_layers;        /* 6 */
@@ -231,6 +232,14 @@ int odam_op_attention_ex(const void* Q, int ldq, const void* K, int ldk, const v
  * dtype 0 fp32 / 1 bf16, gamma / beta / pos fp32; y = LN(x + r) * gamma + beta, y_pos[row] = y[row] + pos[row % L] */
 int odam_op_add_layernorm_ex(const void* x, const void* r, const float* gamma, const float* beta, void* y,
                              const float* pos, int L, void* y_pos, int M, int dtype, void* stream);
+/* The detector's attention at any head width it builds: head_dim 32 or 64, dtype 0 fp32 / 1 bf16 (row pitches multiples of 4 /
+ * 8 elements, ldo of 4), key_mask [dev][B][Lk] nullable; scale float32(sqrt(1 / head_dim)); the kernel the forward would choose
+ * (att.x3 / att.bf16_mfma apply).  Head h at columns h * head_dim ..  At head_dim 32 the same launches as odam_op_attention_ex. */
+int odam_op_attention_hd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                         int B, int H, int Lq, int Lk, int head_dim, int dtype, const unsigned char* key_mask, void* stream);
+/* odam_op_add_layernorm_ex over C channels, C a multiple of 64 in 128 .. 1024 (C = 256: the same kernel as _ex) */
+int odam_op_add_layernorm_c(const void* x, const void* r, const float* gamma, const float* beta, void* y,
+                            const float* pos, int L, void* y_pos, int M, int C, int dtype, void* stream);
 /* MXFP8 tensors (format above).  n elements, n % 32 == 0: x [dev] fp32 (src_dtype 0) or bf16 (1) -> q [dev][n] + s [dev][n / 32] */
 int odam_op_quantize_mxfp8(const void* x, int src_dtype, long long n, void* q, void* s, void* stream);
 int odam_op_dequantize_mxfp8(const void* q, const void* s, long long n, float* y, void* stream);

@@ -6,24 +6,26 @@
 
 namespace odam_dk {
 
-// Fused multi-head attention, head dim 32 (hidden 256 / 8 heads, transformer.py:138-139):
-//   O[b, q, h*32:(h+1)*32] = softmax_k( (Q[b,q,h] / sqrt(32)) . K[b,k,h] ) V[b,k,h]
-// Q/K/V/O are addressed as base + (b*L + row) * ld + h*32, so fused projection buffers work.
+// Fused multi-head attention, head dim D = 32 (hidden 256 / 8 heads, transformer.py:138-139) or 64 (hidden_dim / nheads = 64):
+//   O[b, q, h*D:(h+1)*D] = softmax_k( (Q[b,q,h] * sqrt(1/D)) . K[b,k,h] ) V[b,k,h]
+// Q/K/V/O are addressed as base + (b*L + row) * ld + h*D, so fused projection buffers work.
 // key_mask (nullable) [B][Lk]: non-zero = padded key, left out of the softmax (key_padding_mask, transformer.py:157-160).
 int launch_attention(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
-                     int B, int H, int Lq, int Lk, int dtype, hipStream_t stream, const unsigned char* key_mask = nullptr);
+                     int B, int H, int Lq, int Lk, int dtype, hipStream_t stream, const unsigned char* key_mask = nullptr,
+                     int head_dim = 32);
 
 // same kernel with head dimension 64, fp32 (associator GNN, 4 heads of 64; scores scaled by 1/8)
 int launch_attention_d64(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                          int B, int H, int Lq, int Lk, hipStream_t stream);
 
-// y = LayerNorm(x + r) * gamma + beta over C = 256 (eps 1e-5); r may be null.
+// y = LayerNorm(x + r) * gamma + beta over C channels (eps 1e-5); r may be null.  C = 256 (the default model) or any
+// multiple of 64 in 128 .. 1024 (its own kernel).
 // If y_pos != null also writes y_pos = y + pos[row % L]  (the next layer's q/k input).
 int launch_add_layernorm(const void* x, const void* r, const float* gamma, const float* beta, void* y,
-                         const float* pos, int L, void* y_pos, int M, int dtype, hipStream_t stream);
+                         const float* pos, int L, void* y_pos, int M, int dtype, hipStream_t stream, int C = 256);
 
-// out[m] = (x ? x[m] : 0) + pos[m % L], rows of 256 floats
-int launch_add_pos(const void* x, const float* pos, int L, void* out, int M, int dtype, hipStream_t stream);
+// out[m] = (x ? x[m] : 0) + pos[m % L], rows of C floats (C % 4 == 0; C = 256 has its own kernel)
+int launch_add_pos(const void* x, const float* pos, int L, void* out, int M, int dtype, hipStream_t stream, int C = 256);
 
 // fp32 [B,3,H,W] -> [B,H,W,4] fp32 (4th channel zero) or [B,H,W,8] bf16 (one 16-byte chunk per pixel)
 int launch_nchw_to_nhwc4(const float* in, void* out, int B, int H, int W, int dtype, hipStream_t stream);

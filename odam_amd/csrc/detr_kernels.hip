@@ -526,29 +526,389 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
     }
 }
 
+// =================================================================================================
+// Head dim 64 (hidden_dim / nheads = 64): attention_bf16_kernel and attention_x3_kernel restated for 64 channels per head.
+// Same dataflow, rounding points and softmax; per key tile 4 k-steps of S^T = K . Q^T instead of 2 and two 32-channel output
+// tiles of O^T.  K / V rows are 128 bytes in LDS: K chunk c of key r sits at c ^ ((r >> 1) & 7) (two keys per 256-byte bank
+// row: the ds_read_b128 lane groups stay conflict-free), and a V row keeps its two 64-byte halves swapped where bit 1 of the key
+// is set (the four keys of a transposed read then cover all 64 banks).  At twice the head width a score tile feeds twice the
+// matrix work per exponential.  The D = 32 kernels above are left as they are.
+// =================================================================================================
+// score of a key outside the softmax in attention_bf16_d64_kernel: -2^100 (below the running max's start, -1e30).  The exponent is
+// fma(s, c, -m c) with c = 0.125 log2 e: for s = m = -1e30 that is the rounding error of the product, about 1e22 -- exp2 of it is
+// inf where it is positive, and a leading tile with every key padded would poison the row.  s c is exact at a power of two, so a
+// padded key gives fma(s, c, -m c) <= -0.27e30 c: p = 0
+constexpr float ATT_DEAD64 = -1267650600228229401496703205376.0f;
+__device__ __forceinline__ int att_kswz64(int r, int c) { return r * 8 + (c ^ ((r >> 1) & 7)); }     // 16-byte chunk c of key r
+__device__ __forceinline__ int att_vswz64(int r, int c) { return r * 8 + (c ^ (((r >> 1) & 1) << 2)); }
+// byte offset of this lane's transposed V read for output tile o (as attention_bf16_kernel's tr_off, 128-byte rows; the 64-byte
+// half holding tile o is o ^ (bit 1 of the lane's key row q = (lane & 15) >> 2))
+__device__ __forceinline__ int att_tr_off64(int lane, int o) {
+    return (((lane >> 5) * 4 + ((lane & 15) >> 2)) * 128) + (((o ^ ((lane >> 3) & 1)) * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2);
+}
+
+__global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* __restrict__ Q, int ldq,
+                                                                 const bf16_t* __restrict__ K, int ldk,
+                                                                 const bf16_t* __restrict__ V, int ldv,
+                                                                 bf16_t* __restrict__ O, int ldo, int Lq, int Lk, float c_log2,
+                                                                 const unsigned char* __restrict__ key_mask) {
+    constexpr int KT = 64, D = 64;
+    constexpr int NC = D / 8;            // 16-byte chunks per K / V row
+    constexpr int NS = D / 16;           // 16-channel k-steps of S^T = K . Q^T
+    constexpr int NO = D / 32;           // 32-channel output tiles
+    constexpr int RPP = 256 / NC;        // key rows staged per loader pass
+    constexpr int NLD = KT / RPP;        // loader passes per tile
+    __shared__ __align__(16) uint4 Ks[2][KT * NC];
+    // V row-major with its 64-byte halves swapped as att_vswz64 places them, read transposed (ds_read_b64_tr_b16) as in attention_bf16_kernel
+    __shared__ __align__(16) uint4 Vs[2][KT * NC];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = lane >> 5, col = lane & 31;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int q0 = blockIdx.x * 128 + wave * 32;
+    const bf16_t* Qb = Q + (size_t)b * Lq * ldq + h * D;
+    const bf16_t* Kb = K + (size_t)b * Lk * ldk + h * D;
+    const bf16_t* Vb = V + (size_t)b * Lk * ldv + h * D;
+
+    uint4 qf[NS];    // B operand of S^T = K . Q^T: lane (query col, half) holds Q[q][16 s + 8 half .. + 7]
+    {
+        const int q = q0 + col;
+#pragma unroll
+        for (int st = 0; st < NS; st++)
+            qf[st] = (q < Lq) ? *reinterpret_cast<const uint4*>(Qb + (size_t)q * ldq + 16 * st + 8 * half) : uint4{0u, 0u, 0u, 0u};
+    }
+    const int lk = tid >> 3, lc = tid & 7;         // loader: key row of the tile, 8-channel chunk
+    auto load_kv = [&](int kt, uint4 (&kr)[NLD], uint4 (&vr)[NLD]) {
+#pragma unroll
+        for (int pss = 0; pss < NLD; pss++) {
+            const int key = kt * KT + lk + pss * RPP;
+            if (key < Lk) {
+                kr[pss] = *reinterpret_cast<const uint4*>(Kb + (size_t)key * ldk + lc * 8);
+                vr[pss] = *reinterpret_cast<const uint4*>(Vb + (size_t)key * ldv + lc * 8);
+            } else {
+                kr[pss] = uint4{0u, 0u, 0u, 0u}; vr[pss] = uint4{0u, 0u, 0u, 0u};
+            }
+        }
+    };
+    auto store_kv = [&](int buf, const uint4 (&kr)[NLD], const uint4 (&vr)[NLD]) {
+#pragma unroll
+        for (int pss = 0; pss < NLD; pss++) {
+            const int r = lk + pss * RPP;
+            Ks[buf][att_kswz64(r, lc)] = kr[pss];
+            Vs[buf][att_vswz64(r, lc)] = vr[pss];
+        }
+    };
+    typedef short tr4_t __attribute__((ext_vector_type(4)));
+    int tr_off[NO];
+#pragma unroll
+    for (int o = 0; o < NO; o++) tr_off[o] = att_tr_off64(lane, o);
+
+    floatx16 oacc[NO];
+#pragma unroll
+    for (int o = 0; o < NO; o++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) oacc[o][r] = 0.0f;
+    float m_run = -1e30f, l_run = 0.0f;
+    const int ntiles = (Lk + KT - 1) / KT;
+    uint4 kr[NLD], vr[NLD];
+    load_kv(0, kr, vr);
+    store_kv(0, kr, vr);
+    __syncthreads();
+    for (int kt = 0; kt < ntiles; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < ntiles) load_kv(kt + 1, kr, vr);
+        floatx16 s[2];
+#pragma unroll
+        for (int jh = 0; jh < 2; jh++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) s[jh][r] = 0.0f;
+            const int key = jh * 32 + col;
+#pragma unroll
+            for (int st = 0; st < NS; st++) {
+                const uint4 kf = Ks[cur][att_kswz64(key, 2 * st + half)];
+                s[jh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, kf), __builtin_bit_cast(bf16x8_t, qf[st]),
+                                                                s[jh], 0, 0, 0);
+            }
+        }
+        const int kbase = kt * KT;
+        if (kbase + KT > Lk || key_mask) {
+            const unsigned char* mk = key_mask ? key_mask + (size_t)b * Lk + kbase : nullptr;
+#pragma unroll
+            for (int jh = 0; jh < 2; jh++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int k = jh * 32 + acc_row(r, half);
+                    if (kbase + k >= Lk || (mk && mk[k])) s[jh][r] = ATT_DEAD64;
+                }
+        }
+        float mx = s[0][0];
+#pragma unroll
+        for (int jh = 0; jh < 2; jh++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) mx = fmaxf(mx, s[jh][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c_log2);
+        const float mc = m_new * c_log2;
+        float psum = 0.0f;
+#pragma unroll
+        for (int jh = 0; jh < 2; jh++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                s[jh][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[jh][r], c_log2, -mc));
+                psum += s[jh][r];
+            }
+        psum += __shfl_xor(psum, 32);
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) oacc[o][r] *= alpha;
+#pragma unroll
+        for (int jh = 0; jh < 2; jh++)
+#pragma unroll
+            for (int st = 0; st < 2; st++) {
+                unsigned pw[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    pw[e] = pack_bf16x2(s[jh][8 * st + 2 * e], s[jh][8 * st + 2 * e + 1]);
+                typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
+#pragma unroll
+                for (int o = 0; o < NO; o++) {
+                    const char* vb = reinterpret_cast<const char*>(&Vs[cur][0]) + (jh * 32 + 16 * st) * 2 * D + tr_off[o];
+                    const tr4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb));                  // keys 4 half .. + 3 of the step
+                    const tr4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 2 * D));      // keys 8 + 4 half .. + 3
+                    const uint2 lo = __builtin_bit_cast(uint2, lo4), hi = __builtin_bit_cast(uint2, hi4);
+                    const uint4 vf = uint4{lo.x, lo.y, hi.x, hi.y};
+                    oacc[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vf),
+                                                                      __builtin_bit_cast(bf16x8_t, uint4{pw[0], pw[1], pw[2], pw[3]}), oacc[o], 0, 0, 0);
+                }
+            }
+        if (kt + 1 < ntiles) store_kv(cur ^ 1, kr, vr);
+        __syncthreads();
+    }
+    const int q = q0 + col;
+    if (q < Lq) {
+        const float inv = 1.0f / l_run;
+        bf16_t* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+                st4(Ob + o * 32 + 8 * g + 4 * half,
+                    float4{oacc[o][4 * g + 0] * inv, oacc[o][4 * g + 1] * inv, oacc[o][4 * g + 2] * inv, oacc[o][4 * g + 3] * inv});
+    }
+}
+
+__global__ __launch_bounds__(256) void attention_x3_d64_kernel(const float* __restrict__ Q, int ldq,
+                                                               const float* __restrict__ K, int ldk,
+                                                               const float* __restrict__ V, int ldv,
+                                                               float* __restrict__ O, int ldo, int Lq, int Lk, float scale,
+                                                               const unsigned char* __restrict__ key_mask) {
+    // 32-key tiles: the K / V images (three bf16 planes each, double buffered) stay at attention_x3_kernel's 48 KiB, so three
+    // workgroups still share a CU; 256 chunks of 8 values per tile, one per thread
+    constexpr int D = 64, KT = 32;
+    static_assert(KT == 32, "one 32-key block per tile (the key mask below selects on s[0] only)");
+    constexpr int NJ = KT / 32;          // 32-key blocks per tile
+    constexpr int NC = D / 8;            // 16-byte (bf16) chunks per K / V row
+    constexpr int NS = D / 16;           // 16-channel k-steps of S^T = K . Q^T
+    constexpr int NO = D / 32;           // 32-channel output tiles
+    __shared__ __align__(16) uint4 Ks[2][3][KT * NC];
+    __shared__ __align__(16) uint4 Vs[2][3][KT * NC];     // V's three planes row-major, read transposed (ds_read_b64_tr_b16) as in attention_bf16_kernel
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = lane >> 5, col = lane & 31;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int q0 = blockIdx.x * 128 + wave * 32;
+    const float* Qb = Q + (size_t)b * Lq * ldq + h * D;
+    const float* Kb = K + (size_t)b * Lk * ldk + h * D;
+    const float* Vb = V + (size_t)b * Lk * ldv + h * D;
+
+    uint4 qh[NS], qm[NS], ql[NS];     // B operand of S^T = K . Q^T: lane (query col, half) holds Q[q][16 s + 8 half .. + 7], pre-scaled
+    {
+        const int q = q0 + col;
+#pragma unroll
+        for (int st = 0; st < NS; st++) {
+            float4 a = float4{0.f, 0.f, 0.f, 0.f}, c = a;
+            if (q < Lq) {
+                a = ld4(Qb + (size_t)q * ldq + 16 * st + 8 * half);
+                c = ld4(Qb + (size_t)q * ldq + 16 * st + 8 * half + 4);
+            }
+            a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;
+            c.x *= scale; c.y *= scale; c.z *= scale; c.w *= scale;
+            att_split8(a, c, qh[st], qm[st], ql[st]);
+        }
+    }
+    const int lk = tid >> 3, lc = tid & 7;         // loader: key row of the tile, 8-channel chunk
+    auto load_kv = [&](int kt, float4 (&kr)[2], float4 (&vr)[2]) {
+        const int key = kt * KT + lk;
+        if (key < Lk) {
+            kr[0] = ld4(Kb + (size_t)key * ldk + lc * 8); kr[1] = ld4(Kb + (size_t)key * ldk + lc * 8 + 4);
+            vr[0] = ld4(Vb + (size_t)key * ldv + lc * 8); vr[1] = ld4(Vb + (size_t)key * ldv + lc * 8 + 4);
+        } else {
+            kr[0] = kr[1] = vr[0] = vr[1] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto store_kv = [&](int buf, const float4 (&kr)[2], const float4 (&vr)[2]) {
+        uint4 p[3];
+        att_split8(kr[0], kr[1], p[0], p[1], p[2]);
+#pragma unroll
+        for (int pl = 0; pl < 3; pl++) Ks[buf][pl][att_kswz64(lk, lc)] = p[pl];
+        att_split8(vr[0], vr[1], p[0], p[1], p[2]);
+#pragma unroll
+        for (int pl = 0; pl < 3; pl++) Vs[buf][pl][att_vswz64(lk, lc)] = p[pl];
+    };
+    typedef short tr4_t __attribute__((ext_vector_type(4)));
+    typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
+    int tr_off[NO];
+#pragma unroll
+    for (int o = 0; o < NO; o++) tr_off[o] = att_tr_off64(lane, o);
+#define ODAM_MMA(acc, a, bq) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, bq), acc, 0, 0, 0)
+
+    floatx16 oacc[NO];
+#pragma unroll
+    for (int o = 0; o < NO; o++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) oacc[o][r] = 0.0f;
+    float m_run = -1e30f, l_run = 0.0f;
+    const int ntiles = (Lk + KT - 1) / KT;
+    float4 kr[2], vr[2];
+    load_kv(0, kr, vr);
+    store_kv(0, kr, vr);
+    __syncthreads();
+    for (int kt = 0; kt < ntiles; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < ntiles) load_kv(kt + 1, kr, vr);
+        floatx16 s[NJ];
+#pragma unroll
+        for (int jh = 0; jh < NJ; jh++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) s[jh][r] = 0.0f;
+            const int key = jh * 32 + col;
+#pragma unroll
+            for (int st = 0; st < NS; st++) {
+                const int idx = att_kswz64(key, 2 * st + half);
+                const uint4 kh = Ks[cur][0][idx], km = Ks[cur][1][idx], kl = Ks[cur][2][idx];
+                ODAM_MMA(s[jh], kl, qh[st]); ODAM_MMA(s[jh], km, qm[st]); ODAM_MMA(s[jh], kh, ql[st]);     // smallest products first
+                ODAM_MMA(s[jh], km, qh[st]); ODAM_MMA(s[jh], kh, qm[st]);
+                ODAM_MMA(s[jh], kh, qh[st]);
+            }
+        }
+        const int kbase = kt * KT;
+        // keys beyond Lk and padded keys: one bit per accumulator register, gathered first and applied by selects (written
+        // inside the branch, the stores to the accumulator were lost in code generation at this tile size)
+        unsigned dead = 0u;
+        if (kbase + KT > Lk || key_mask) {
+            const unsigned char* mk = key_mask ? key_mask + (size_t)b * Lk + kbase : nullptr;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int k = acc_row(r, half);
+                if (kbase + k >= Lk || (mk && mk[k])) dead |= 1u << r;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) s[0][r] = ((dead >> r) & 1u) ? -1e30f : s[0][r];
+        float mx = s[0][0];
+#pragma unroll
+        for (int jh = 0; jh < NJ; jh++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) mx = fmaxf(mx, s[jh][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __expf(m_run - m_new);
+        float psum = 0.0f;
+#pragma unroll
+        for (int jh = 0; jh < NJ; jh++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                s[jh][r] = __expf(s[jh][r] - m_new);
+                psum += s[jh][r];
+            }
+        psum += __shfl_xor(psum, 32);
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) oacc[o][r] *= alpha;
+        // O^T += V^T . P^T: the accumulator registers 8 st .. 8 st + 7 of s[jh], split, are the B operand of k-step (jh, st)
+#pragma unroll
+        for (int jh = 0; jh < NJ; jh++)
+#pragma unroll
+            for (int st = 0; st < 2; st++) {
+                uint4 ph, pm, pl_;
+                att_split8(float4{s[jh][8 * st + 0], s[jh][8 * st + 1], s[jh][8 * st + 2], s[jh][8 * st + 3]},
+                           float4{s[jh][8 * st + 4], s[jh][8 * st + 5], s[jh][8 * st + 6], s[jh][8 * st + 7]}, ph, pm, pl_);
+#pragma unroll
+                for (int o = 0; o < NO; o++) {
+                    uint4 vf[3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; pl++) {
+                        const char* vb = reinterpret_cast<const char*>(&Vs[cur][pl][0]) + (jh * 32 + 16 * st) * 2 * D + tr_off[o];
+                        const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb)));
+                        const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 2 * D)));
+                        vf[pl] = uint4{lo.x, lo.y, hi.x, hi.y};
+                    }
+                    ODAM_MMA(oacc[o], vf[2], ph); ODAM_MMA(oacc[o], vf[1], pm); ODAM_MMA(oacc[o], vf[0], pl_);
+                    ODAM_MMA(oacc[o], vf[1], ph); ODAM_MMA(oacc[o], vf[0], pm);
+                    ODAM_MMA(oacc[o], vf[0], ph);
+                }
+            }
+        if (kt + 1 < ntiles) store_kv(cur ^ 1, kr, vr);
+        __syncthreads();
+    }
+#undef ODAM_MMA
+    const int q = q0 + col;
+    if (q < Lq) {
+        const float inv = 1.0f / l_run;
+        float* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+                st4(Ob + o * 32 + 8 * g + 4 * half,
+                    float4{oacc[o][4 * g + 0] * inv, oacc[o][4 * g + 1] * inv, oacc[o][4 * g + 2] * inv, oacc[o][4 * g + 3] * inv});
+    }
+}
+
 int launch_attention(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
-                     int B, int H, int Lq, int Lk, int dtype, hipStream_t stream, const unsigned char* key_mask) {
+                     int B, int H, int Lq, int Lk, int dtype, hipStream_t stream, const unsigned char* key_mask, int head_dim) {
     if (Lq <= 0 || Lk <= 0 || B <= 0) return 0;
+    if (head_dim != 32 && head_dim != 64) return odam_fail(1, "launch_attention: head dim 32 or 64 only");
     dim3 grid((Lq + 127) / 128, H, B);
-    const float scale = (float)0.1767766952966369;   // sqrt(1/32) as torch computes it in float64, then float32
+    // sqrt(1/D) as torch computes it in float64, then float32 (F.multi_head_attention_forward: q * float(head_dim) ** -0.5)
+    const float scale = head_dim == 32 ? (float)0.1767766952966369 : 0.125f;
     const bool bf16_mfma = odam_cfg::get(odam_cfg::ATT_BF16_MFMA) != 0;   // 0: keep bf16 mode on the fp32-instruction kernel
     if (dtype == 1 && bf16_mfma && (ldq % 8) == 0 && (ldk % 8) == 0 && (ldv % 8) == 0 && (ldo % 4) == 0) {
-        hipLaunchKernelGGL(attention_bf16_kernel, grid, dim3(256), 0, stream, (const bf16_t*)Q, ldq, (const bf16_t*)K, ldk,
-                           (const bf16_t*)V, ldv, (bf16_t*)O, ldo, Lq, Lk, scale * 1.44269504088896341f, key_mask);
+        if (head_dim == 32)
+            hipLaunchKernelGGL(attention_bf16_kernel, grid, dim3(256), 0, stream, (const bf16_t*)Q, ldq, (const bf16_t*)K, ldk,
+                               (const bf16_t*)V, ldv, (bf16_t*)O, ldo, Lq, Lk, scale * 1.44269504088896341f, key_mask);
+        else
+            hipLaunchKernelGGL(attention_bf16_d64_kernel, grid, dim3(256), 0, stream, (const bf16_t*)Q, ldq, (const bf16_t*)K, ldk,
+                               (const bf16_t*)V, ldv, (bf16_t*)O, ldo, Lq, Lk, scale * 1.44269504088896341f, key_mask);
         ODAM_HIP(hipGetLastError());
         return 0;
     }
     // fp32: products through the exact three-way bf16 split (ODAM_ATT_X3=0 keeps the fp32 matrix instruction)
     const bool x3 = odam_cfg::get(odam_cfg::ATT_X3) != 0;
     if (dtype == 0 && x3 && (ldq % 4) == 0 && (ldk % 4) == 0 && (ldv % 4) == 0 && (ldo % 4) == 0) {
-        hipLaunchKernelGGL(attention_x3_kernel, grid, dim3(256), 0, stream, (const float*)Q, ldq, (const float*)K, ldk,
-                           (const float*)V, ldv, (float*)O, ldo, Lq, Lk, scale, key_mask);
+        if (head_dim == 32)
+            hipLaunchKernelGGL(attention_x3_kernel, grid, dim3(256), 0, stream, (const float*)Q, ldq, (const float*)K, ldk,
+                               (const float*)V, ldv, (float*)O, ldo, Lq, Lk, scale, key_mask);
+        else
+            hipLaunchKernelGGL(attention_x3_d64_kernel, grid, dim3(256), 0, stream, (const float*)Q, ldq, (const float*)K, ldk,
+                               (const float*)V, ldv, (float*)O, ldo, Lq, Lk, scale, key_mask);
         ODAM_HIP(hipGetLastError());
         return 0;
     }
+    if (head_dim == 32) {
 #define ODAM_K(T, ...) hipLaunchKernelGGL((attention_kernel<T, 32>), grid, dim3(256), 0, stream, (const T*)Q, ldq, (const T*)K, ldk, (const T*)V, ldv, (T*)O, ldo, Lq, Lk, scale, key_mask)
-    ODAM_DISPATCH(dtype, ODAM_K, 0);
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
 #undef ODAM_K
+    } else {
+#define ODAM_K(T, ...) hipLaunchKernelGGL((attention_kernel<T, 64>), grid, dim3(256), 0, stream, (const T*)Q, ldq, (const T*)K, ldk, (const T*)V, ldv, (T*)O, ldo, Lq, Lk, scale, key_mask)
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
+#undef ODAM_K
+    }
     ODAM_HIP(hipGetLastError());
     return 0;
 }
@@ -603,12 +963,81 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const T* __restrict_
     }
 }
 
+// the same over any C = 64 n, n = 2 .. 16 (transformer widths other than 256): one wavefront per row, channel 64 j + lane in
+// register j (coalesced 64-element rows), two-pass statistics of the row shifted by its first value
+constexpr int LN_MAXJ = 16;
+
+template <typename T>
+__global__ __launch_bounds__(256) void add_layernorm_c_kernel(const T* __restrict__ x, const T* __restrict__ r,
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, T* __restrict__ y,
+                                                              const float* __restrict__ pos, int L,
+                                                              T* __restrict__ y_pos, int M, int C) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const int nj = C >> 6;
+    const size_t base = (size_t)row * C + lane;
+    auto ld1 = [](const T* p) -> float {
+        if constexpr (sizeof(T) == 2) return bf2f(*p);
+        else return *p;
+    };
+    auto st1 = [](T* p, float v) {
+        if constexpr (sizeof(T) == 2) *p = f2bf(v);
+        else *p = v;
+    };
+    float v[LN_MAXJ];
+#pragma unroll
+    for (int j = 0; j < LN_MAXJ; j++) {
+        v[j] = 0.0f;
+        if (j < nj) {
+            v[j] = ld1(x + base + 64 * j);
+            if (r) v[j] += ld1(r + base + 64 * j);
+        }
+    }
+    // statistics of v - v0 (v0 = the row's channel 0): C need not be a power of two, so a constant row summed as it stands would
+    // not return its value as the mean; shifted, it sums to exactly 0 and the output is beta, as the C = 256 kernel gives it
+    const float v0 = __shfl(v[0], 0);
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < LN_MAXJ; j++) {
+        v[j] -= v0;
+        if (j < nj) s += v[j];
+    }
+    const float inv_c = 1.0f / (float)C;
+    const float mean = wave_sum(s) * inv_c;
+    float q = 0.0f;
+#pragma unroll
+    for (int j = 0; j < LN_MAXJ; j++) {
+        v[j] -= mean;
+        if (j < nj) q += v[j] * v[j];
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_c + 1e-5f);
+    const float* pr = y_pos ? pos + (size_t)(row % L) * C + lane : nullptr;
+#pragma unroll
+    for (int j = 0; j < LN_MAXJ; j++) {
+        if (j < nj) {
+            const int c = 64 * j + lane;
+            const float o = v[j] * rstd * gamma[c] + beta[c];
+            st1(y + base + 64 * j, o);
+            if (y_pos) st1(y_pos + base + 64 * j, o + pr[64 * j]);
+        }
+    }
+}
+
 int launch_add_layernorm(const void* x, const void* r, const float* gamma, const float* beta, void* y,
-                         const float* pos, int L, void* y_pos, int M, int dtype, hipStream_t stream) {
+                         const float* pos, int L, void* y_pos, int M, int dtype, hipStream_t stream, int C) {
     if (M <= 0) return 0;
+    if (C == 256) {
 #define ODAM_K(T, ...) hipLaunchKernelGGL(add_layernorm_kernel<T>, dim3((M + 3) / 4), dim3(256), 0, stream, (const T*)x, (const T*)r, gamma, beta, (T*)y, pos, L, (T*)y_pos, M)
-    ODAM_DISPATCH(dtype, ODAM_K, 0);
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
 #undef ODAM_K
+    } else {
+        if (C % 64 || C < 128 || C > 64 * LN_MAXJ) return odam_fail(1, "launch_add_layernorm: C must be a multiple of 64 in 128 .. 1024");
+#define ODAM_K(T, ...) hipLaunchKernelGGL(add_layernorm_c_kernel<T>, dim3((M + 3) / 4), dim3(256), 0, stream, (const T*)x, (const T*)r, gamma, beta, (T*)y, pos, L, (T*)y_pos, M, C)
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
+#undef ODAM_K
+    }
     ODAM_HIP(hipGetLastError());
     return 0;
 }
@@ -627,12 +1056,35 @@ __global__ __launch_bounds__(256) void add_pos_kernel(const T* __restrict__ x, c
     st4(out + i * 4, p);
 }
 
-int launch_add_pos(const void* x, const float* pos, int L, void* out, int M, int dtype, hipStream_t stream) {
+// rows of C4 = C / 4 four-channel groups (any C % 4 == 0)
+template <typename T>
+__global__ __launch_bounds__(256) void add_pos_c_kernel(const T* __restrict__ x, const float* __restrict__ pos,
+                                                        int L, T* __restrict__ out, int M, int C4) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // float4 index
+    if (i >= (size_t)M * C4) return;
+    const int row = (int)(i / C4), c4 = (int)(i - (size_t)row * C4);
+    float4 p = *reinterpret_cast<const float4*>(pos + ((size_t)(row % L) * C4 + c4) * 4);
+    if (x) {
+        const float4 v = ld4(x + i * 4);
+        p.x += v.x; p.y += v.y; p.z += v.z; p.w += v.w;
+    }
+    st4(out + i * 4, p);
+}
+
+int launch_add_pos(const void* x, const float* pos, int L, void* out, int M, int dtype, hipStream_t stream, int C) {
     if (M <= 0) return 0;
-    const size_t n4 = (size_t)M * 64;
+    if (C == 256) {
+        const size_t n4 = (size_t)M * 64;
 #define ODAM_K(T, ...) hipLaunchKernelGGL(add_pos_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const T*)x, pos, L, (T*)out, M)
-    ODAM_DISPATCH(dtype, ODAM_K, 0);
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
 #undef ODAM_K
+    } else {
+        if (C <= 0 || C % 4) return odam_fail(1, "launch_add_pos: C must be a positive multiple of 4");
+        const size_t n4 = (size_t)M * (C / 4);
+#define ODAM_K(T, ...) hipLaunchKernelGGL(add_pos_c_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const T*)x, pos, L, (T*)out, M, C / 4)
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
+#undef ODAM_K
+    }
     ODAM_HIP(hipGetLastError());
     return 0;
 }

@@ -79,8 +79,8 @@ struct odam_detr {
     Conv class_embed;
     Conv mlp[5][3];  // bbox, offset, angle, size, depth
     Conv stem_rows;              // fp32: conv1 as a 7x1 convolution over 32-float rows of the framed NHWC4 image (see forward_impl)
-    float* pos = nullptr;        // [L, 256]
-    float* query_pos = nullptr;  // [Q, 256]
+    float* pos = nullptr;        // [L, hidden_dim]
+    float* query_pos = nullptr;  // [Q, hidden_dim]
 
     // geometry
     int H1, W1, H2, W2, fh, fw, L;
@@ -257,8 +257,21 @@ int fold_bn(odam_detr* m, Conv& c, const std::string& prefix) {
 
 int pack_ln(odam_detr* m, LN& ln, const std::string& prefix) {
     NEED(w, prefix + ".weight"); NEED(b, prefix + ".bias");
+    if (w->data.size() != (size_t)m->cfg.hidden_dim || b->data.size() != (size_t)m->cfg.hidden_dim) {
+        std::snprintf(g_odam_err, sizeof(g_odam_err), "odam_detr_finalize: %s must have hidden_dim = %d entries", prefix.c_str(),
+                      m->cfg.hidden_dim);
+        return 1;
+    }
     if (int rc = m->upload(&ln.g, w->data)) return rc;
     return m->upload(&ln.b, b->data);
+}
+
+// nn.MultiheadAttention's packed projection of a hidden_dim-wide model: weight [3 E, E], bias [3 E]
+int check_in_proj(const HostTensor& w, const HostTensor& b, int E, const std::string& name) {
+    if (w.shape.size() == 2 && w.shape[0] == 3LL * E && w.shape[1] == E && b.data.size() == 3 * (size_t)E) return 0;
+    std::snprintf(g_odam_err, sizeof(g_odam_err), "odam_detr_finalize: %s.in_proj_weight must be [%d, %d] (hidden_dim %d)", name.c_str(),
+                  3 * E, E, E);
+    return 1;
 }
 
 // a filter of the BasicBlock plan has the shape that plan reads ([Cout, Cin, k, k]): a Bottleneck checkpoint under a BasicBlock
@@ -280,6 +293,14 @@ int run_conv(const Conv& c, const void* x, int B, int H, int W, const void* res,
     a.Cout = c.Cout; a.KH = c.KH; a.KW = c.KW; a.stride = c.stride; a.pad = c.pad; a.Kpad = c.Kpad; a.dil = c.dil;
     a.relu = relu ? 1 : 0; a.M = B * a.Ho * a.Wo; a.ldc = ldc > 0 ? ldc : c.Cout;
     a.k_order = c.k_order;
+    if (c.KH * c.KW == 1 && (c.Cin & (c.Cin - 1))) {
+        // one tap whose width is not a power of two (linears of a 192 / 320 / 384 ... wide transformer): the gather splits k into
+        // tap and channel with a power-of-two Cin, so give it the next one -- k < Kpad = Cin stays inside tap 0 -- and the real
+        // pixel stride in lda
+        int p2 = 1;
+        while (p2 < c.Cin) p2 <<= 1;
+        a.Cin = p2; a.log2Cin = ilog2(p2); a.lda = c.Cin;
+    }
     return odam_cg::launch_conv_gemm(a, st);
 }
 
@@ -437,7 +458,8 @@ int mx_t(odam_detr* m, const Conv& c, const unsigned char* x, const unsigned cha
 }
 int att_t(odam_detr* m, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
           int B, int H, int Lq, int Lk, hipStream_t st, const unsigned char* key_mask = nullptr) {
-    if (!m->profile) return odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, m->dt, st, key_mask);
+    const int hd = m->cfg.hidden_dim / m->cfg.nheads;      // 32 or 64 (odam_detr_create)
+    if (!m->profile) return odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, m->dt, st, key_mask, hd);
     if (m->aev_used + 2 > m->aev.size()) {
         for (int k = 0; k < 2; k++) {
             hipEvent_t e;
@@ -446,9 +468,9 @@ int att_t(odam_detr* m, const void* Q, int ldq, const void* K, int ldk, const vo
         }
         m->aev_flops.resize(m->aev.size() / 2);
     }
-    m->aev_flops[m->aev_used / 2] = 4.0 * B * H * (double)Lq * Lk * 32;   // QK^T + PV, 2 flop per MAC
+    m->aev_flops[m->aev_used / 2] = 4.0 * B * H * (double)Lq * Lk * hd;   // QK^T + PV, 2 flop per MAC
     ODAM_HIP(hipEventRecord(m->aev[m->aev_used], st));
-    int rc = odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, m->dt, st, key_mask);
+    int rc = odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, m->dt, st, key_mask, hd);
     ODAM_HIP(hipEventRecord(m->aev[m->aev_used + 1], st));
     m->aev_used += 2;
     return rc;
@@ -458,8 +480,13 @@ int att_t(odam_detr* m, const void* Q, int ldq, const void* K, int ldk, const vo
 
 extern "C" int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out) {
     if (!cfg || !out) return odam_fail(1, "odam_detr_create: null argument");
-    if (cfg->hidden_dim != 256 || cfg->nheads != 8)
-        return odam_fail(3, "odam_detr_create: kernels are built for hidden_dim 256, 8 heads (head dim 32)");
+    // transformer widths: the attention kernels take head dim 32 or 64, the LayerNorm kernels 64 n channels, n = 2 .. 16
+    if (cfg->hidden_dim % 64 || cfg->hidden_dim < 128 || cfg->hidden_dim > 1024)
+        return odam_fail(3, "odam_detr_create: hidden_dim must be a multiple of 64 in 128 .. 1024");
+    if (cfg->nheads < 1 || cfg->hidden_dim % cfg->nheads)
+        return odam_fail(3, "odam_detr_create: hidden_dim must be a multiple of nheads");
+    if (cfg->hidden_dim / cfg->nheads != 32 && cfg->hidden_dim / cfg->nheads != 64)
+        return odam_fail(3, "odam_detr_create: head dim hidden_dim / nheads must be 32 or 64 (16 and 128 are not built)");
     if (cfg->max_batch < 1 || cfg->img_h < 32 || cfg->img_w < 32) return odam_fail(1, "odam_detr_create: bad sizes");
     if (cfg->dtype < 0 || cfg->dtype > 2) return odam_fail(1, "odam_detr_create: dtype must be 0 (fp32), 1 (bf16) or 2 (mxfp8)");
     if (cfg->dtype == 2 && cfg->dilation)
@@ -607,6 +634,7 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
         const std::string p = "transformer.encoder.layers." + std::to_string(i) + ".";
         EncLayer e;
         NEED(ipw, p + "self_attn.in_proj_weight"); NEED(ipb, p + "self_attn.in_proj_bias");
+        RC(check_in_proj(*ipw, *ipb, E, p + "self_attn"));
         RC(pack_linear(m, e.qk, *ipw, ipb, 0, 2 * E));
         RC(pack_linear(m, e.v, *ipw, ipb, 2 * E, 3 * E));
         NEED(ow, p + "self_attn.out_proj.weight"); NEED(ob, p + "self_attn.out_proj.bias");
@@ -626,11 +654,13 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
         const std::string p = "transformer.decoder.layers." + std::to_string(i) + ".";
         DecLayer d;
         NEED(ipw, p + "self_attn.in_proj_weight"); NEED(ipb, p + "self_attn.in_proj_bias");
+        RC(check_in_proj(*ipw, *ipb, E, p + "self_attn"));
         RC(pack_linear(m, d.qk, *ipw, ipb, 0, 2 * E));
         RC(pack_linear(m, d.v, *ipw, ipb, 2 * E, 3 * E));
         NEED(ow, p + "self_attn.out_proj.weight"); NEED(ob, p + "self_attn.out_proj.bias");
         RC(pack_linear(m, d.out, *ow, ob, 0, E));
         NEED(cw, p + "multihead_attn.in_proj_weight"); NEED(cb, p + "multihead_attn.in_proj_bias");
+        RC(check_in_proj(*cw, *cb, E, p + "multihead_attn"));
         RC(pack_linear(m, d.cq, *cw, cb, 0, E));
         kall.data.insert(kall.data.end(), cw->data.begin() + (size_t)E * E, cw->data.begin() + (size_t)2 * E * E);
         vall.data.insert(vall.data.end(), cw->data.begin() + (size_t)2 * E * E, cw->data.begin() + (size_t)3 * E * E);
@@ -661,6 +691,7 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
                 RC(pack_linear(m, m->mlp[k][j], *lw, lb, 0, (int)lw->shape[0]));
             }
         NEED(q, "query_embed.weight");
+        if (q->data.size() != (size_t)c.num_queries * E) return odam_fail(1, "query_embed.weight must be [num_queries, hidden_dim]");
         RC(m->upload(&m->query_pos, q->data));
         NEED(pe, "pos_embed");
         if ((int)pe->shape[0] != m->L || (int)pe->shape[1] != E) return odam_fail(1, "pos_embed must be [h*w, hidden_dim]");
@@ -838,19 +869,19 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
     RC(conv_t(m, m->input_proj, cur, B, H, W, nullptr, false, m->src, st));
     const float* pos = pos_b ? pos_b : m->pos;     // row r of the batch reads pos[r % Lp]
     const int Lp = pos_b ? M : L;
-    RC(odam_dk::launch_add_pos(m->src, pos, Lp, m->srcpos, M, dt, st));
+    RC(odam_dk::launch_add_pos(m->src, pos, Lp, m->srcpos, M, dt, st, E));
     const void* memory_p = m->src;      // the encoder's output (pre_norm: after its final LayerNorm, in tmp)
     for (size_t i = 0; i < m->enc.size(); i++) {
         const EncLayer& e = m->enc[i];
         if (c.pre_norm) {
             // forward_pre (transformer.py:169-183): src2 = norm1(src); q = k = src2 + pos; src += attn(q, k, src2);
             //                                       src2 = norm2(src); src += linear2(relu(linear1(src2)))
-            RC(odam_dk::launch_add_layernorm(m->src, nullptr, e.n1.g, e.n1.b, m->tmp, pos, Lp, m->srcpos, M, dt, st));
+            RC(odam_dk::launch_add_layernorm(m->src, nullptr, e.n1.g, e.n1.b, m->tmp, pos, Lp, m->srcpos, M, dt, st, E));
             RC(lin_t(m, e.qk, m->srcpos, M, nullptr, false, m->qk, st));
             RC(lin_t(m, e.v, m->tmp, M, nullptr, false, m->v, st));
             RC(att_t(m, m->qk, 2 * E, off(m->qk, E), 2 * E, m->v, E, m->att, E, B, Hh, L, L, st, key_mask));
             RC(lin_t(m, e.out, m->att, M, m->src, false, m->src, st));                  // residual added in place
-            RC(odam_dk::launch_add_layernorm(m->src, nullptr, e.n2.g, e.n2.b, m->tmp, nullptr, L, nullptr, M, dt, st));
+            RC(odam_dk::launch_add_layernorm(m->src, nullptr, e.n2.g, e.n2.b, m->tmp, nullptr, L, nullptr, M, dt, st, E));
             RC(lin_t(m, e.l1, m->tmp, M, nullptr, true, m->ffn, st));
             RC(lin_t(m, e.l2, m->ffn, M, m->src, false, m->src, st));
             continue;
@@ -859,13 +890,13 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
         RC(lin_t(m, e.v, m->src, M, nullptr, false, m->v, st));
         RC(att_t(m, m->qk, 2 * E, off(m->qk, E), 2 * E, m->v, E, m->att, E, B, Hh, L, L, st, key_mask));
         RC(lin_t(m, e.out, m->att, M, m->src, false, m->tmp, st));
-        RC(odam_dk::launch_add_layernorm(m->tmp, nullptr, e.n1.g, e.n1.b, m->src, nullptr, L, nullptr, M, dt, st));
+        RC(odam_dk::launch_add_layernorm(m->tmp, nullptr, e.n1.g, e.n1.b, m->src, nullptr, L, nullptr, M, dt, st, E));
         RC(lin_t(m, e.l1, m->src, M, nullptr, true, m->ffn, st));
         RC(lin_t(m, e.l2, m->ffn, M, m->src, false, m->tmp, st));
-        RC(odam_dk::launch_add_layernorm(m->tmp, nullptr, e.n2.g, e.n2.b, m->src, pos, Lp, m->srcpos, M, dt, st));
+        RC(odam_dk::launch_add_layernorm(m->tmp, nullptr, e.n2.g, e.n2.b, m->src, pos, Lp, m->srcpos, M, dt, st, E));
     }
     if (c.pre_norm) {      // memory = encoder.norm(src) (transformer.py:82-83), memory + pos for the cross-attention keys
-        RC(odam_dk::launch_add_layernorm(m->src, nullptr, m->enc_norm.g, m->enc_norm.b, m->tmp, pos, Lp, m->srcpos, M, dt, st));
+        RC(odam_dk::launch_add_layernorm(m->src, nullptr, m->enc_norm.g, m->enc_norm.b, m->tmp, pos, Lp, m->srcpos, M, dt, st, E));
         memory_p = m->tmp;
     }
     m->memory_out = memory_p;
@@ -875,22 +906,22 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
 
     // ---- decoder (transformer.py:217-238) --------------------------------------------------------
     ODAM_HIP(hipMemsetAsync(m->tgt, 0, es * (size_t)Mq * E, st));
-    RC(odam_dk::launch_add_pos(nullptr, m->query_pos, Q, m->tgtpos, Mq, dt, st));
+    RC(odam_dk::launch_add_pos(nullptr, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
     const int ldkv = c.dec_layers * E;
     for (size_t i = 0; i < m->dec.size(); i++) {
         const DecLayer& d = m->dec[i];
         if (c.pre_norm) {
             // forward_pre (transformer.py:240-262): every sub-block normalises its INPUT and adds its output to tgt
-            RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n1.g, d.n1.b, m->dtmp, m->query_pos, Q, m->tgtpos, Mq, dt, st));
+            RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n1.g, d.n1.b, m->dtmp, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
             RC(lin_t(m, d.qk, m->tgtpos, Mq, nullptr, false, m->dqk, st));
             RC(lin_t(m, d.v, m->dtmp, Mq, nullptr, false, m->dv, st));
             RC(att_t(m, m->dqk, 2 * E, off(m->dqk, E), 2 * E, m->dv, E, m->datt, E, B, Hh, Q, Q, st));
             RC(lin_t(m, d.out, m->datt, Mq, m->tgt, false, m->tgt, st));
-            RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n2.g, d.n2.b, m->dtmp, m->query_pos, Q, m->tgtpos, Mq, dt, st));
+            RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n2.g, d.n2.b, m->dtmp, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
             RC(lin_t(m, d.cq, m->tgtpos, Mq, nullptr, false, m->dq, st));
             RC(att_t(m, m->dq, E, off(m->kc, i * E), ldkv, off(m->vc, i * E), ldkv, m->datt, E, B, Hh, Q, L, st, key_mask));
             RC(lin_t(m, d.cout, m->datt, Mq, m->tgt, false, m->tgt, st));
-            RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n3.g, d.n3.b, m->dtmp, nullptr, Q, nullptr, Mq, dt, st));
+            RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n3.g, d.n3.b, m->dtmp, nullptr, Q, nullptr, Mq, dt, st, E));
             RC(lin_t(m, d.l1, m->dtmp, Mq, nullptr, true, m->dffn, st));
             RC(lin_t(m, d.l2, m->dffn, Mq, m->tgt, false, m->tgt, st));
             continue;
@@ -899,18 +930,18 @@ static int forward_impl(odam_detr* m, const float* img, int B, const unsigned ch
         RC(lin_t(m, d.v, m->tgt, Mq, nullptr, false, m->dv, st));
         RC(att_t(m, m->dqk, 2 * E, off(m->dqk, E), 2 * E, m->dv, E, m->datt, E, B, Hh, Q, Q, st));
         RC(lin_t(m, d.out, m->datt, Mq, m->tgt, false, m->dtmp, st));
-        RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n1.g, d.n1.b, m->tgt, m->query_pos, Q, m->tgtpos, Mq, dt, st));
+        RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n1.g, d.n1.b, m->tgt, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
         RC(lin_t(m, d.cq, m->tgtpos, Mq, nullptr, false, m->dq, st));
         RC(att_t(m, m->dq, E, off(m->kc, i * E), ldkv, off(m->vc, i * E), ldkv, m->datt, E, B, Hh, Q, L, st, key_mask));
         RC(lin_t(m, d.cout, m->datt, Mq, m->tgt, false, m->dtmp, st));
-        RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n2.g, d.n2.b, m->tgt, nullptr, Q, nullptr, Mq, dt, st));
+        RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n2.g, d.n2.b, m->tgt, nullptr, Q, nullptr, Mq, dt, st, E));
         RC(lin_t(m, d.l1, m->tgt, Mq, nullptr, true, m->dffn, st));
         RC(lin_t(m, d.l2, m->dffn, Mq, m->tgt, false, m->dtmp, st));
-        RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n3.g, d.n3.b, m->tgt, m->query_pos, Q, m->tgtpos, Mq, dt, st));
+        RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n3.g, d.n3.b, m->tgt, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
     }
     // fp32 mode: the final norm can write straight into the caller's obj_features buffer
     void* hs = (obj_features && dt == 0) ? (void*)obj_features : (void*)m->hs;
-    RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, m->dec_norm.g, m->dec_norm.b, hs, nullptr, Q, nullptr, Mq, dt, st));
+    RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, m->dec_norm.g, m->dec_norm.b, hs, nullptr, Q, nullptr, Mq, dt, st, E));
     if (obj_features && dt != 0) RC(odam_dk::launch_to_f32(m->hs, obj_features, (size_t)Mq * E, dt, st));
 
     // ---- heads on the last decoder layer (detr.py:73-88); their outputs are fp32 in every mode ----
@@ -1169,6 +1200,31 @@ extern "C" int odam_op_add_layernorm_ex(const void* x, const void* r, const floa
     if (dtype != 0 && dtype != 1) return odam_fail(1, "odam_op_add_layernorm_ex: dtype must be 0 (fp32) or 1 (bf16)");
     if (M < 0) return odam_fail(1, "odam_op_add_layernorm_ex: negative M");
     return odam_dk::launch_add_layernorm(x, r, gamma, beta, y, pos, y_pos ? L : 1, y_pos, M, dtype, (hipStream_t)stream);
+}
+
+// the detector's attention at either head width (the model's own launcher and kernel choice)
+extern "C" int odam_op_attention_hd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                                    int B, int H, int Lq, int Lk, int head_dim, int dtype, const unsigned char* key_mask,
+                                    void* stream) {
+    if (!Q || !K || !V || !O) return odam_fail(1, "odam_op_attention_hd: null pointer");
+    if (B < 0 || H < 0 || Lq < 0 || Lk < 0) return odam_fail(1, "odam_op_attention_hd: negative extent");
+    if (head_dim != 32 && head_dim != 64) return odam_fail(1, "odam_op_attention_hd: head_dim must be 32 or 64");
+    if (dtype != 0 && dtype != 1) return odam_fail(1, "odam_op_attention_hd: dtype must be 0 (fp32) or 1 (bf16)");
+    const int pm = dtype == 1 ? 8 : 4;
+    if (ldq % pm || ldk % pm || ldv % pm || ldo % 4)
+        return odam_fail(1, "odam_op_attention_hd: row pitches must be multiples of 8 / 8 / 8 / 4 (bf16) or 4 (fp32) elements");
+    if (H == 0) return 0;
+    return odam_dk::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Lq, Lk, dtype, (hipStream_t)stream, key_mask, head_dim);
+}
+
+extern "C" int odam_op_add_layernorm_c(const void* x, const void* r, const float* gamma, const float* beta, void* y,
+                                       const float* pos, int L, void* y_pos, int M, int C, int dtype, void* stream) {
+    if (!x || !gamma || !beta || !y) return odam_fail(1, "odam_op_add_layernorm_c: null pointer");
+    if (y_pos && (!pos || L <= 0)) return odam_fail(1, "odam_op_add_layernorm_c: y_pos needs pos and L > 0");
+    if (dtype != 0 && dtype != 1) return odam_fail(1, "odam_op_add_layernorm_c: dtype must be 0 (fp32) or 1 (bf16)");
+    if (M < 0) return odam_fail(1, "odam_op_add_layernorm_c: negative M");
+    if (C % 64 || C < 128 || C > 1024) return odam_fail(1, "odam_op_add_layernorm_c: C must be a multiple of 64 in 128 .. 1024");
+    return odam_dk::launch_add_layernorm(x, r, gamma, beta, y, pos, y_pos ? L : 1, y_pos, M, dtype, (hipStream_t)stream, C);
 }
 
 extern "C" int odam_op_maxpool3x3s2_nhwc(const float* x, float* y, int B, int H, int W, int C, void* stream) {

@@ -7,6 +7,7 @@ reference keeps on the host (thresholding, greedy nms_3d, list-of-numpy packagin
 161-205) plus the constant sine position embedding (position_encoding.py:26-46)."""
 import ctypes
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -62,13 +63,25 @@ def sine_position_embedding(h, w, num_pos_feats=128, temperature=10000, mask=Non
 
 
 def learned_position_embedding(row_embed, col_embed, h, w):
-    """PositionEmbeddingLearned for an h x w grid -> [h*w, 256] float32 (position_encoding.py:49-74): token (y, x) carries
+    """PositionEmbeddingLearned for an h x w grid -> [h*w, hidden_dim] float32 (position_encoding.py:49-74): token (y, x) carries
     cat(col_embed[x], row_embed[y]); the tables hold 50 rows (h, w <= 50), and the padding mask plays no part."""
     if h > row_embed.shape[0] or w > col_embed.shape[0]:
         raise _lib.OdamError("learned position embedding: the token grid exceeds the embedding tables (50 x 50)")
     x_emb, y_emb = col_embed[:w], row_embed[:h]
     pos = torch.cat([x_emb.unsqueeze(0).repeat(h, 1, 1), y_emb.unsqueeze(1).repeat(1, w, 1)], dim=-1)
     return pos.reshape(h * w, -1).to(torch.float32).contiguous()
+
+
+def check_transformer_width(hidden_dim, nheads):
+    """the transformer widths the kernels are built for (src/models/transformer.py takes any d_model / nhead): hidden_dim a
+    multiple of 64 in 128 .. 1024, divisible by nheads, head dim hidden_dim / nheads 32 or 64 (16 and 128 are not built)"""
+    if not (isinstance(hidden_dim, numbers.Integral) and hidden_dim % 64 == 0 and 128 <= hidden_dim <= 1024):
+        raise ValueError(f"hidden_dim={hidden_dim!r}: must be a multiple of 64 in 128 .. 1024")
+    if not (isinstance(nheads, numbers.Integral) and nheads >= 1 and hidden_dim % nheads == 0):
+        raise ValueError(f"nheads={nheads!r}: hidden_dim={hidden_dim} must be a multiple of nheads")
+    if hidden_dim // nheads not in (32, 64):
+        raise ValueError(f"hidden_dim={hidden_dim}, nheads={nheads}: head dim hidden_dim / nheads = {hidden_dim // nheads} must be "
+                         "32 or 64 (head dims 16 and 128 are not built)")
 
 
 class Detector:
@@ -94,6 +107,7 @@ class Detector:
             raise ValueError("dtype must be 'fp32' (parity mode), 'bf16' (BASELINE config 4) or 'mxfp8' (MXFP8 ResNet body)")
         if dtype == "mxfp8" and dilation:
             raise ValueError("dtype='mxfp8': dilation (DC5) is not supported in the mxfp8 mode")
+        check_transformer_width(hidden_dim, nheads)
         self.dtype = dtype
         self.arch = dict(backbone=backbone, hidden_dim=hidden_dim, nheads=nheads, dim_feedforward=dim_feedforward,
                          enc_layers=enc_layers, dec_layers=dec_layers, num_queries=num_queries,
@@ -293,7 +307,7 @@ class Detector:
         return res
 
     def debug_taps(self, B, H, W):
-        """layer4 feature map [B,C4,h,w] (C4 = 2048 Bottleneck, 512 BasicBlock backbones) and encoder memory [B,h*w,256] of the
+        """layer4 feature map [B,C4,h,w] (C4 = 2048 Bottleneck, 512 BasicBlock backbones) and encoder memory [B,h*w,hidden_dim] of the
         last forward (tests)."""
         hd = self._handle(H, W)
         L = _lib.lib()

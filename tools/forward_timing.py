@@ -2,6 +2,7 @@
 """Forward wall time of the detector per arithmetic mode, with the per-stage totals of its contraction launches.
 
    python tools/forward_timing.py --backbone resnet101 --batch 32 --size 800 1066 --dtypes fp32 bf16 mxfp8 [--steps 10 --warmup 3]
+                                  [--hidden-dim 512 --nheads 8]
 
 One JSON line per dtype: the median wall time of --steps forwards after --warmup (the stream synchronised around each), then one
 profiled forward's totals (Detector.profile_read_stages: stem, layer1 .. layer4, rest = input_proj + transformer projections /
@@ -25,14 +26,17 @@ def main():
     ap.add_argument("--dtypes", nargs="+", default=["bf16", "mxfp8"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--hidden-dim", type=int, default=256, help="transformer width (a multiple of 64 in 128 .. 1024)")
+    ap.add_argument("--nheads", type=int, default=8, help="attention heads (head dim hidden_dim / nheads: 32 or 64)")
     a = ap.parse_args()
     import torch
     from odam_amd import detector, weights
     H, W = a.size
-    sd = weights.make_state_dict(backbone=a.backbone, seed=0)
+    sd = weights.make_state_dict(backbone=a.backbone, hidden=a.hidden_dim, seed=0)
     img = torch.randn(a.batch, 3, H, W, generator=torch.Generator().manual_seed(0)).to("cuda:0")
     for dt in a.dtypes:
-        det = detector.Detector(backbone=a.backbone, max_batch=a.batch, device="cuda:0", n_streams=1, dtype=dt)
+        det = detector.Detector(backbone=a.backbone, hidden_dim=a.hidden_dim, nheads=a.nheads, max_batch=a.batch, device="cuda:0",
+                                n_streams=1, dtype=dt)
         det.load_state_dict(sd)
         for _ in range(a.warmup):
             det(img)
@@ -51,12 +55,12 @@ def main():
         det.profile(H, W, False)
         det.close()
         print(json.dumps({
-            "backbone": a.backbone, "batch": a.batch, "size": [H, W], "dtype": dt,
+            "backbone": a.backbone, "hidden_dim": a.hidden_dim, "nheads": a.nheads, "batch": a.batch, "size": [H, W], "dtype": dt,
             "forward_ms_median": round(statistics.median(times), 3), "forward_ms_min": round(min(times), 3),
             "frames_per_s": round(a.batch * 1e3 / statistics.median(times), 1), "steps": a.steps, "warmup": a.warmup,
             "stages": {k: {"launches": n, "ms": round(ms, 3), "tflops": round(fl / ms / 1e9, 1) if ms > 0 else 0.0}
                        for k, (n, ms, fl) in stages.items()},
-            "attention": {"launches": na, "ms": round(ams, 3)},
+            "attention": {"launches": na, "ms": round(ams, 3), "tflops": round(afl / ams / 1e9, 1) if ams > 0 else 0.0},
         }), flush=True)
 
 
