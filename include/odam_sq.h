@@ -102,6 +102,34 @@ int odam_sq_oriented_bbox(const float* points, int n_obj, int n_pts, double* cor
 /* the hull alone (tests): hull [host][n_pts] <- point indices in the order of scipy's ConvexHull(points[:, :2]).vertices */
 int odam_sq_hull2d(const float* points, int n_pts, int* hull, int* n_hull, int* status);
 
+/*
+ * The reference's second object model, QuadricOptimizer.run (src/super_quadric/sq_libs.py:194-241): the dual quadric
+ * Q = T diag((scale_factor * h)^2, -1) T^T, T = [rotz(angle) | translate], fitted to the bbox edges of its projected conics
+ * C = M Q M^T by n_iters Adam steps (lr 0.01, no prior).  ONE launch for all objects, one wavefront per object, views strided
+ * over the lanes; stream-ordered, and no allocation except that the handle's bias-correction table for this path grows
+ * (hipMalloc, a synchronisation of the caller's stream if an older table is replaced) the first time more steps are asked for.
+ * Nothing odam_sq_create uploaded is touched; n_iters is NOT bounded by the context's max_iters.
+ *   init5        [dev] [n_obj][5]   translate[3], angle, scale_factor (the reference starts at 1)
+ *   half_dims    [dev] [n_obj][3]   h = dims / 2 as float32 (constant)
+ *   view_offsets, P, tgt, mask      as odam_sq_fit_batch (tgt in pixels, order x_min, x_max, y_min, y_max)
+ *   max_views    largest view count of any object, 1 .. 16 * ODAM_SQ_MAX_VIEWS, else ODAM_E_LIMIT
+ *   out5         [dev] [n_obj][5]
+ *   out_Q        [dev] [n_obj][16]  row-major params2mat of out5 (float32, not symmetrised: as the reference's product)
+ *   loss_log     [dev] [n_obj][n_iters]     loss_2d per step; nullable
+ *   traj         [dev] [n_obj][n_iters][5]  parameters after every step; nullable
+ *   status       [dev] [n_obj][2]   code, step:  0, -1 = fitted;  1, s = a view's discriminant 4 C_i2^2 - 4 C_ii C_22 was
+ *                negative (or NaN) at step s (0-based) -- where the reference asserts (sq_libs.py:129,136): the object keeps the
+ *                parameters it had before that step, its loss_log rows from s on are NaN and its traj rows repeat them;
+ *                2, 0 = the object's view count is outside 1 .. max_views (nothing fitted).  Other objects are unaffected.
+ * odam_dq_set_group_waves: objects per workgroup (1, 2, 4 or 8; default 4) -- scheduling only, every result is bit-identical.
+ * DualQuadric.get_srt / compute_ellipsoid_points (sq_libs.py:257-348) are NOT in this library: LAPACK's geev decides the
+ * eigenvector bits in the reference (scipy.linalg.eig), so odam_amd/sq.py calls the same scipy routine on the host.
+ */
+int odam_dq_fit_batch(odam_sq_ctx* ctx, int n_obj, const float* init5, const float* half_dims, const int* view_offsets,
+                      const float* P, const float* tgt, const float* mask, int n_iters, int max_views, float* out5,
+                      float* out_Q, float* loss_log, float* traj, int* status, void* stream);
+int odam_dq_set_group_waves(odam_sq_ctx* ctx, int waves);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@
 #include "odam_config.h"
 #include "odam_err.h"
 #include "sq_core.h"
+#include "dq_ctx.h"
 
 namespace {
 using namespace odam_sq;
@@ -894,7 +895,10 @@ struct odam_sq_ctx {
     int* d_order = nullptr;
     int* h_order = nullptr;       // pinned staging of the same size (the upload is stream-ordered: no NULL-stream copy that would wait for other streams)
     size_t order_n = 0;
+    odam_dq_state dq;             // the dual-quadric fit's own Adam table (dq_fit.hip); nothing of the fields above is shared with it
 };
+
+odam_dq_state* odam_sq_ctx_dq(odam_sq_ctx* ctx) { return &ctx->dq; }
 
 static std::vector<float> sampler_draws() {
     // sampling.cpp:18-28 with seed 0 (_sampler.pyx:438): identical generator, identical draws
@@ -955,6 +959,8 @@ extern "C" int odam_sq_destroy(odam_sq_ctx* c) {
         if (c->d_proj_pts) (void)hipFree(c->d_proj_pts);
         if (c->d_cam) (void)hipFree(c->d_cam);
         c->d_proj_pts = nullptr; c->d_cam = nullptr;
+        if (c->dq.d_adam) (void)hipFree(c->dq.d_adam);
+        c->dq.d_adam = nullptr;
     }
     if (!c) return ODAM_OK;
     (void)hipFree(c->d_draws);

@@ -257,6 +257,33 @@ def default_fitter(device="cuda:0"):
     return _DEFAULT_FITTER[device]
 
 
+def _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, fit_mask, n_iters, fitter, return_params):
+    """The fit and result half of optim_process for representation "dual_quadric": all eligible objects in one fit_dual call
+    (an object whose discriminant goes negative raises AssertionError there, as sq_libs.py:129,136 does), DualQuadric results,
+    bboxes_qc from compute_oriented_bbox of the 2500 ellipsoid points (run_multi_view.py:66-67) through the native box path."""
+    n_objs = len(tracks)
+    params = {i: inits[i][0] for i in range(n_objs)}
+    Qs = {}
+    if fit_ids:
+        out = fitter.fit_dual(np.stack([inits[i][0] for i in fit_ids]), np.stack([inits[i][1] for i in fit_ids]), fit_counts,
+                              np.concatenate(fit_P), np.concatenate(fit_tgt), np.concatenate(fit_mask), n_iters=n_iters)
+        fp, fq = out["params"].cpu().numpy(), out["Q"].cpu().numpy()
+        for j, i in enumerate(fit_ids):
+            params[i] = fp[j]
+            Qs[i] = fq[j]
+    quadrics = [_sq.DualQuadric(Qs[i] if i in Qs else _sq.dual_params2mat(*inits[i])) for i in range(n_objs)]
+    boxes = {}
+    if fit_ids:
+        bl, _ = compute_oriented_bboxes(np.stack([quadrics[i].compute_ellipsoid_points(use_numpy=True)[0] for i in fit_ids]))
+        boxes = dict(zip(fit_ids, bl))
+    bboxes_qc = [boxes[i] if i in boxes else bboxes_dl[i] for i in range(n_objs)]
+    out_dict = {"tracks": tracks, "bboxes_qc": bboxes_qc, "bboxes_dl": bboxes_dl, "quadrics": quadrics}
+    if return_params:
+        out_dict["params"] = np.stack([params[i] for i in range(n_objs)]) if n_objs else np.zeros((0, 5), np.float32)
+        out_dict["fitted"] = np.array([i in Qs for i in range(n_objs)], bool)
+    return out_dict
+
+
 def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representation, prior, n_iters, n_views,
                   fitter=None, return_params=False):
     """run_multi_view.py:22-76 with the per-object fits batched on the GPU."""
@@ -285,9 +312,12 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
         scales = np.mean(np.asarray(dims), axis=0)
         bboxes_dl.append(get_3d_box(scales, T_wo[:3, :3], T_wo[:3, 3]))
         yaw = yaws[obj_id] if yaws is not None else Rotation.from_matrix(T_wo[:3, :3]).as_euler("zxy")[0]
-        if prior and obj_class not in _sq.CLASS_MAPPER:
-            raise KeyError(obj_class)  # sq_libs.py:464 (CLASS_MAPPER covers classes 0..7 only)
-        inits.append(_sq.init_params(T_wo[:3, 3], yaw, scales, representation))
+        if representation == "dual_quadric":      # QuadricOptimizer.__init__ (sq_libs.py:41-58): no class, no prior
+            inits.append(_sq.init_dual(T_wo[:3, 3], yaw, scales))
+        else:
+            if prior and obj_class not in _sq.CLASS_MAPPER:
+                raise KeyError(obj_class)  # sq_libs.py:464 (CLASS_MAPPER covers classes 0..7 only)
+            inits.append(_sq.init_params(T_wo[:3, 3], yaw, scales, representation))
         classes.append(obj_class)
         valid = mask.any(axis=1)       # frames with at least one constrained edge (run_multi_view.py:51-54)
         if int(valid.sum()) >= n_views:
@@ -297,6 +327,8 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
             fit_mask.append(mask[valid])
             fit_counts.append(int(valid.sum()))
 
+    if representation == "dual_quadric":
+        return _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, fit_mask, n_iters, fitter, return_params)
     params = {i: inits[i] for i in range(n_objs)}
     points = {}
     if fit_ids:

@@ -608,8 +608,10 @@ class OdamProcess:
 
     def optim_process(self, tracks, return_params=False):
         m = self.sequence_meta
+        # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
+        n_iters = 500 if self.representation == "dual_quadric" else 200
         return multi_view.optim_process(tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
-                                        self.representation, prior=True, n_iters=200, n_views=10,
+                                        self.representation, prior=True, n_iters=n_iters, n_views=10,
                                         fitter=self._fitter(), return_params=return_params)
 
     def optim_process_params(self, tracks):

@@ -19,7 +19,8 @@ N_POINTS = 1000
 WG_VIEWS = 1024          # rows one workgroup reduces (ODAM_SQ_MAX_VIEWS)
 MAX_VIEWS = 16 * WG_VIEWS  # per object: split over up to 16 workgroups
 NAMES = ("x_min", "x_max", "y_min", "y_max")  # sq_libs.py:438
-REPRESENTATIONS = {"super_quadric": 0, "cube": 1, "quadric": 2}
+REPRESENTATIONS = {"super_quadric": 0, "cube": 1, "quadric": 2, "dual_quadric": 3}   # 0..2: odam_sq_fit_batch codes; 3: fit_dual
+DQ_POINTS = 2500         # 50 x 50 angle grid of DualQuadric.compute_ellipsoid_points (sq_libs.py:325)
 # sq_libs.py:13-22
 CLASS_MAPPER = {0: "03211117", 1: "04379243", 2: "02808440", 3: "02747177",
                 4: "04256520", 5: "03001627", 6: "02933112", 7: "02871439"}
@@ -193,6 +194,55 @@ class SqFitter:
             self._last = (stream, ev)
         return {"params": out_p, "points": out_pts, "loss": loss, "traj": traj}
 
+    def fit_dual(self, init5, half_dims, view_counts, P, tgt, mask, n_iters=500, want_loss=False, want_traj=False,
+                 check=True):
+        """Batched QuadricOptimizer.run (sq_libs.py:194-241): every object through all its steps in ONE launch.
+
+        init5 [n,5] f32 (translate[3], angle, scale_factor); half_dims [n,3] f32 (= dims / 2); view_counts [n];
+        P [sumF,3,4]/[sumF,12], tgt, mask [sumF,4] f32.  Returns dict: params [n,5], Q [n,4,4] (device tensors), status
+        [n,2] int32 numpy (code, step), loss / traj when asked for.  With check (default) an object whose discriminant
+        went negative raises AssertionError, where the reference asserts (sq_libs.py:129,136)."""
+        dev = self.device
+        n = len(view_counts)
+        vc = np.asarray(view_counts, np.int64)
+        if n == 0:
+            return {"params": torch.zeros(0, 5, device=dev), "Q": torch.zeros(0, 4, 4, device=dev), "status": np.zeros((0, 2), np.int32),
+                    "loss": None, "traj": None}
+        if vc.min() < 1 or vc.max() > MAX_VIEWS:
+            raise _lib.OdamError(f"views per object must be in 1..{MAX_VIEWS}, got {vc.min()}..{vc.max()}")
+        as_dev = lambda x, dt: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=dev, dtype=dt).contiguous()
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum(vc)
+        d_p0 = as_dev(init5, torch.float32).reshape(n, 5)
+        d_h = as_dev(half_dims, torch.float32).reshape(n, 3)
+        d_off = as_dev(offs, torch.int32)
+        d_P = as_dev(P, torch.float32).reshape(-1, 12)
+        d_t = as_dev(tgt, torch.float32).reshape(-1, 4)
+        d_m = as_dev(mask, torch.float32).reshape(-1, 4)
+        assert d_P.shape[0] == offs[-1] and d_t.shape[0] == offs[-1] and d_m.shape[0] == offs[-1]
+        n_iters = int(n_iters)
+        out_p = torch.empty(n, 5, device=dev, dtype=torch.float32)
+        out_Q = torch.empty(n, 4, 4, device=dev, dtype=torch.float32)
+        status = torch.empty(n, 2, device=dev, dtype=torch.int32)
+        loss = torch.empty(n, n_iters, device=dev, dtype=torch.float32) if want_loss else None
+        traj = torch.empty(n, n_iters, 5, device=dev, dtype=torch.float32) if want_traj else None
+        with torch.cuda.device(dev), self._lock:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().odam_dq_fit_batch(
+                self._h, ctypes.c_int(n), _lib.ptr(d_p0), _lib.ptr(d_h), _lib.ptr(d_off), _lib.ptr(d_P), _lib.ptr(d_t), _lib.ptr(d_m),
+                ctypes.c_int(n_iters), ctypes.c_int(int(vc.max())), _lib.ptr(out_p), _lib.ptr(out_Q), _lib.ptr(loss), _lib.ptr(traj),
+                _lib.ptr(status), ctypes.c_void_p(stream)), "odam_dq_fit_batch")
+        st = status.cpu().numpy()
+        if check:
+            bad = np.flatnonzero(st[:, 0] != 0)
+            # the reference's only error path: `assert not torch.isnan(b_x).any()`
+            assert len(bad) == 0, "dual-quadric fit: negative discriminant (object, step): %s" % [(int(i), int(st[i, 1])) for i in bad]
+        return {"params": out_p, "Q": out_Q, "status": st, "loss": loss, "traj": traj}
+
+    def set_dual_group_waves(self, waves):
+        """objects per workgroup of fit_dual's launch (1, 2, 4, 8): scheduling only, results are bit-identical"""
+        _lib.check(_lib.lib().odam_dq_set_group_waves(self._h, ctypes.c_int(int(waves))), "odam_dq_set_group_waves")
+
     def points(self, params):
         """compute_ellipsoid_points for [n,9] parameter rows -> [n,1000,3] device tensor."""
         dev = self.device
@@ -272,3 +322,71 @@ def host_sample(a, e):
     _lib.check(_lib.lib().odam_sq_sample(a.ctypes.data_as(fp), e.ctypes.data_as(fp), et.ctypes.data_as(fp),
                                          om.ctypes.data_as(fp)), "odam_sq_sample")
     return et, om
+
+
+def init_dual(translate, angle, dims):
+    """QuadricOptimizer.__init__ (sq_libs.py:41-58): (translate[3], angle, scale_factor = 1) and h = dims / 2, float32."""
+    init5 = np.concatenate([np.asarray(translate, np.float64).reshape(3), [float(angle)], [1.0]]).astype(np.float32)
+    return init5, (np.asarray(dims, np.float64).reshape(3) / 2).astype(np.float32)
+
+
+def dual_params2mat(p5, half_dims):
+    """QuadricOptimizer.params2mat (sq_libs.py:68-78) of a float32 state, for objects that were not fitted (Q_init): the
+    reference's own operations -- float32 (T @ diag) @ T.T by the host BLAS."""
+    p = np.asarray(p5, np.float32)
+    a = (p[4] * np.asarray(half_dims, np.float32)) ** 2
+    c, s = np.cos(p[3]), np.sin(p[3])
+    T = np.array([[c, -s, 0, p[0]], [s, c, 0, p[1]], [0, 0, 1, p[2]], [0, 0, 0, 1]], np.float32)
+    return (T @ np.diag(np.concatenate([a, [np.float32(-1)]]).astype(np.float32)) @ T.T).astype(np.float32)
+
+
+class DualQuadric:
+    """The reference's DualQuadric (sq_libs.py:244-348) over a 4x4 float32 matrix.  Host code: get_srt's eigenvector bits are
+    LAPACK's (scipy.linalg.eig, the routine the reference calls), so it stays on scipy rather than in the native library."""
+
+    def __init__(self, Q):
+        self.Q = np.asarray(Q)
+
+    def projection(self, P, if_vectorize=False):
+        return P @ self.Q @ P.T
+
+    def get_srt(self):      # sq_libs.py:257-280
+        import scipy.linalg
+        t_wo = -self.Q[:3, 3:]
+        A = self.Q[:3, :3] + t_wo @ t_wo.T
+        scale, R_wo = scipy.linalg.eig(A)
+        scale = scale.astype(np.float32)      # (drops a zero imaginary part, as upstream)
+        if np.linalg.det(R_wo) < 0:
+            R_wo *= -1
+        is_ellipsoid = not (scale < 0).any()
+        scale = np.abs(scale)
+        return scale, R_wo, t_wo, is_ellipsoid
+
+    def transform(self, T_cw):
+        return T_cw @ self.Q @ T_cw.T
+
+    def get_bbox(self, P, if_vectorize=False, line_form=False):      # sq_libs.py:289-314
+        C = self.projection(P, if_vectorize)
+        with np.errstate(invalid="ignore"):
+            b_x = np.sqrt(4 * C[0, 2] ** 2 - 4 * C[0, 0] * C[2, 2])
+            b_y = np.sqrt(4 * C[1, 2] ** 2 - 4 * C[1, 1] * C[2, 2])
+        x_0, x_1 = 0.5 / C[2, 2] * (2 * C[0, 2] + b_x), 0.5 / C[2, 2] * (2 * C[0, 2] - b_x)
+        y_0, y_1 = 0.5 / C[2, 2] * (2 * C[1, 2] + b_y), 0.5 / C[2, 2] * (2 * C[1, 2] - b_y)
+        x_min, x_max, y_min, y_max = min(x_0, x_1), max(x_0, x_1), min(y_0, y_1), max(y_0, y_1)
+        if line_form:
+            return [np.array([1, 0, -x_min]), np.array([0, 1, -y_min]), np.array([1, 0, -x_max]), np.array([0, 1, -y_max])]
+        return np.array([x_min, y_min, x_max, y_max])
+
+    def compute_ellipsoid_points(self, use_numpy=None):      # sq_libs.py:316-348
+        axes, R, centre, is_ellipsoid = self.get_srt()
+        axes = np.sqrt(axes)
+        centre = centre.flatten()
+        side = 50
+        u = np.linspace(0, 2 * np.pi, side)
+        v = np.linspace(0, np.pi, side)
+        x = axes[0] * np.outer(np.cos(u), np.sin(v))
+        y = axes[1] * np.outer(np.sin(u), np.sin(v))
+        z = axes[2] * np.outer(np.ones_like(u), np.cos(v))
+        x, y, z = np.tensordot(R, np.vstack((x, y, z)).reshape((3, side, side)), axes=1)
+        pts = np.stack([(x + centre[0]).reshape(-1), (y + centre[1]).reshape(-1), (z + centre[2]).reshape(-1)], axis=1)
+        return pts.astype(np.float32), is_ellipsoid
