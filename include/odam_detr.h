@@ -5,7 +5,8 @@
  * (src/processor.py:259-289):
  *   src/models/detr.py:49-94      DETR.forward        -> odam_detr_forward
  *   src/models/detr.py:96-140     DETR.postprocess    -> odam_detr_postprocess (arithmetic per query;
- *                                 thresholding + greedy nms_3d :161-205 stay on the host)
+ *                                 thresholding + greedy nms_3d :161-205 stay on the host: odam_detr_select -- or run on
+ *                                 the device with the rows of run_detector behind them: odam_detr_select_pack)
  *   src/models/backbone.py:21-94  FrozenBatchNorm2d + torchvision ResNet-50/101 body
  *   src/models/transformer.py     6+6 post-norm encoder/decoder, nn.MultiheadAttention(256, 8)
  *   run_processor.py:32-33        load_state_dict      -> odam_detr_set_weight per state_dict entry,
@@ -109,6 +110,26 @@ int odam_detr_postprocess(odam_detr* m, const float* logits, const float* boxes,
 /* Threshold + greedy nms_3d (detr.py:124-125, 161-205) on ONE frame's rows [host][Q,16] as written by
  * odam_detr_postprocess; keep_idx [host][Q] receives the kept query indices in descending-score order. */
 int odam_detr_select(const float* rows, int Q, float threshold, int nms_2d, int* keep_idx, int* n_keep);
+
+/*
+ * The same step for B frames on the device, with the rows of run_detector behind it (detr.py:124-125, 161-205;
+ * src/processor.py:269-288, 318-319): what odam_detr_select, then odam_amd/processor.py::detection_array, then
+ * odam_amd/parallel.py::pack_detections compute on the host, bit for bit, in one launch of one wavefront per frame
+ * (odam_amd/csrc/det_select.hip).  Stream-ordered; allocates nothing, synchronises nothing.
+ *   rows16     [dev][B][Q][16] as written by odam_detr_postprocess, 16-byte aligned; Q <= 256, else ODAM_E_LIMIT (3)
+ *   frame_ids  [dev][B] the frame ids as float32 (column 0 of the rows)
+ *   seq_w/h    the sequence's image size: columns 2-5 are the pixel box divided by it in float32
+ *   sincos     [dev][n_bins][2] float32 sine and cosine of each angle bin, computed by the caller the way the host path
+ *              computes them (odam_amd/detector.py::sincos_table); a bin outside 0 .. n_bins-1 (odam_detr_postprocess
+ *              writes none) gives NaN in columns 12, 13
+ *   det_block  [dev][B][30][15] float32: frame id, class, box / (seq_w, seq_h), dimensions, translate, sin, cos, score of
+ *              the first 30 kept detections in kept order; unused slots hold -1
+ *   det_count  [dev][B] detections kept (<= 30)
+ *   keep_idx   [dev][B][30] their query indices, -1 in unused slots (nullable)
+ */
+int odam_detr_select_pack(const float* rows16, int B, int Q, float threshold, int nms_2d, const float* frame_ids,
+                          float seq_w, float seq_h, const float* sincos, int n_bins, float* det_block, int* det_count,
+                          int* keep_idx, void* stream);
 
 /* The detector's input transform on the device (reference: src/datasets/transforms.py:281-290 = resize :75-105 via
  * torchvision F.resize -> PIL Image.resize(BILINEAR), ToTensor :222-224, Normalize :236-243; called per frame from

@@ -84,6 +84,28 @@ def check_transformer_width(hidden_dim, nheads):
                          "32 or 64 (head dims 16 and 128 are not built)")
 
 
+def sincos_table(n_bins):
+    """[n_bins, 2] float32: sine and cosine of every angle bin as the host path arrives at them -- `select` turns a bin into
+    float32 degrees, processor.detection_array into float32 radians and takes numpy's float32 sine / cosine (columns 12, 13
+    of its rows; the float64 row and the float32 block of parallel.pack_detections hold the same value).  The angle has only
+    n_bins values, so odam_detr_select_pack looks them up here and no device transcendental can differ from numpy's."""
+    angles = (np.arange(n_bins, dtype=np.float32) * np.float32(180 / n_bins)).astype(np.float32)      # select
+    a = np.asarray(angles) / 180. * np.pi                                                             # detection_array
+    return np.ascontiguousarray(np.stack([np.sin(a), np.cos(a)], axis=1), np.float32)
+
+
+# odam_detr_select_pack as include/odam_detr.h declares it (tests/test_select_pack_host.py holds the two together)
+SELECT_PACK_ARGTYPES = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_float,
+                        ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+
+def _select_pack_entry():
+    f = _lib.lib().odam_detr_select_pack
+    if f.argtypes is None:
+        f.argtypes, f.restype = SELECT_PACK_ARGTYPES, ctypes.c_int
+    return f
+
+
 class Detector:
     """DETR forward on the GPU library.  One native handle per input size (the workspace and the
     position table depend on it), created lazily at the first call with that size."""
@@ -117,6 +139,7 @@ class Detector:
         self.device = torch.device(device)
         self._sd = None
         self._handles = {}
+        self._sincos_dev = {}       # (device, angle bins) -> sine / cosine table of select_pack
 
     # ---- nn.Module-like surface used by run_processor.py:30-34 -------------------------------------
     def to(self, device):
@@ -322,8 +345,9 @@ class Detector:
         return l4, mem
 
     # ---- DETR.postprocess (detr.py:96-159) ----------------------------------------------------------
-    def postprocess_rows(self, out, img_size, intr_mat):
-        """device part: [B,Q,16] rows (score, class, box, 3D centre, angle bin, dims) -> numpy"""
+    def postprocess_rows(self, out, img_size, intr_mat, on_device=False):
+        """device part: [B,Q,16] rows (score, class, box, 3D centre, angle bin, dims) -> numpy (on_device: the device tensor, for
+        select_pack)"""
         H, W = out["_hw"]
         h = self._handle(H, W)
         B = out["pred_logits"].shape[0]
@@ -336,6 +360,8 @@ class Detector:
                 _lib.ptr(out["pred_offset"]), _lib.ptr(out["pred_size"]), _lib.ptr(out["pred_depth"]), ctypes.c_int(B),
                 K9.ctypes.data_as(_lib.c_float_p), ctypes.c_float(img_w), ctypes.c_float(img_h), _lib.ptr(rows),
                 ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "odam_detr_postprocess")
+        if on_device:
+            return rows
         return rows.cpu().numpy()
 
     @staticmethod
@@ -353,6 +379,62 @@ class Detector:
                     angles=(r[:, 9] * np.float32(180 / n_bins)).astype(np.float32), translates=r[:, 6:9].copy(),
                     classes=r[:, 1].astype(np.int64), scores=r[:, 0].copy())
 
+    # ---- the same step on the device (opt-in): threshold + NMS + detection rows, nothing comes back to the host -----------
+    def _sincos(self):
+        """the angle bins' sine / cosine table on this detector's device, uploaded once per device"""
+        cache = self._sincos_dev
+        key = (str(self.device), self.arch["angle_bins"])
+        if key not in cache:
+            cache[key] = torch.from_numpy(sincos_table(self.arch["angle_bins"])).to(self.device)
+        return cache[key]
+
+    def _frame_ids_dev(self, frame_ids):
+        """frame ids as the float32 column pack_detections ends up with (float64 in the rows, then the float32 cast)"""
+        if torch.is_tensor(frame_ids):
+            return frame_ids.to(self.device, torch.float32).contiguous()
+        return torch.from_numpy(np.asarray(frame_ids, np.float64).astype(np.float32)).to(self.device)
+
+    def select_pack(self, rows16_dev, frame_ids, seq_size, threshold, nms_2d=True, return_keep=False, out=None, stream=None):
+        """`select` + processor.detection_array + parallel.pack_detections for B frames in one launch (odam_detr_select_pack),
+        bit for bit what that host chain returns.  rows16_dev: [B,Q,16] float32 on the device (postprocess_rows(..., on_device=True));
+        frame_ids: B numbers (or a device tensor); seq_size: (img_w, img_h) of the sequence (sequence_meta), what the pixel boxes
+        are divided by.  Returns device tensors (block float32 [B,30,15], count int32 [B]) -- and keep int32 [B,30], the kept
+        query indices, with return_keep.  Enqueued on `stream` (a raw stream; default: the current one); `out` = (block, count)
+        to write into.  More than 256 queries per frame are an error here: `select` has no such limit."""
+        B, Q = rows16_dev.shape[:2]
+        assert rows16_dev.is_cuda and rows16_dev.dtype == torch.float32 and rows16_dev.is_contiguous() and rows16_dev.shape[2] == 16
+        fid = self._frame_ids_dev(frame_ids)
+        assert fid.shape == (B,)
+        dev = self.device
+        if out is None:
+            out = (torch.empty(B, 30, 15, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.int32))
+        blk, cnt = out
+        keep = torch.empty(B, 30, device=dev, dtype=torch.int32) if return_keep else None
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        seq_w, seq_h = seq_size
+        with torch.cuda.device(dev):
+            _lib.check(_select_pack_entry()(rows16_dev.data_ptr(), B, Q, float(threshold), int(bool(nms_2d)), fid.data_ptr(),
+                                            float(seq_w), float(seq_h), self._sincos().data_ptr(), self.arch["angle_bins"],
+                                            blk.data_ptr(), cnt.data_ptr(), keep.data_ptr() if return_keep else None, st),
+                       "odam_detr_select_pack")
+        return (blk, cnt, keep) if return_keep else (blk, cnt)
+
+    def detect_resident_packed(self, frames, img_size, intr_mat, frame_ids, seq_size, threshold, nms_2d=True, batch=None):
+        """detect_resident_chunks with the host step left out: the same batches on the same streams through the same forward and
+        odam_detr_postprocess calls, and behind each batch, on its stream, odam_detr_select_pack.  Returns device tensors
+        (block float32 [N,30,15], count int32 [N]) -- parallel.pack_detections of the host chain over the same rows, bit for bit --
+        ordered behind the caller's current stream; the [N,Q,16] rows never leave the device and nothing here waits for it.
+        frame_ids: N numbers; seq_size: (img_w, img_h) the boxes are divided by; threshold / nms_2d as `postprocess`."""
+        N = frames.shape[0]
+        dev = self.device
+        pack = dict(frame_ids=self._frame_ids_dev(frame_ids), seq_size=seq_size, threshold=threshold, nms_2d=nms_2d,
+                    out=(torch.empty(N, 30, 15, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.int32)))
+        assert pack["frame_ids"].shape == (N,)
+        self._sincos()      # (uploaded before the streams fork)
+        for _ in self.detect_resident_chunks(frames, img_size, intr_mat, chunk=1 << 30, batch=batch, _pack=pack):
+            pass
+        return pack["out"]
+
     def detect_resident(self, frames, img_size, intr_mat):
         """Forward + per-query post-processing over frames already resident on the device ([N,3,H,W] float32):
         all rows [N,Q,16] as one numpy array (see detect_resident_chunks for the streaming form)."""
@@ -369,7 +451,7 @@ class Detector:
         layer3 / layer4; 0.6-1.8 % over 32)"""
         return 42 if n_frames <= 300 else 38
 
-    def detect_resident_chunks(self, frames, img_size, intr_mat, chunk=128, batch=None):
+    def detect_resident_chunks(self, frames, img_size, intr_mat, chunk=128, batch=None, _pack=None):
         """Forward + per-query post-processing over frames resident in HBM -- or, when `frames` is a (pinned) host
         tensor, uploaded batch by batch on a copy stream into two staging buffers per compute stream, so the
         PCIe transfer of batch n+1 runs under the kernels of batch n -- where (1) batches alternate between `n_streams` HIP streams, each with its own
@@ -379,7 +461,9 @@ class Detector:
         asynchronous copy into pinned host memory + an event), and the generator yields
         (first_frame, rows[n,Q,16]) as each chunk's event completes -- host-side thresholding / NMS of chunk i
         overlaps the kernels of chunks i+1.. .
-        batch: frames per forward (<= max_batch, the default); "auto" = batch_for(number of frames)."""
+        batch: frames per forward (<= max_batch, the default); "auto" = batch_for(number of frames).
+        _pack: detect_resident_packed's arguments -- odam_detr_select_pack follows each batch on its stream, no rows are copied to
+        the host and nothing is yielded."""
         raw = frames.dtype == torch.uint8     # [N,h,w,3] frames as decoded: the input transform runs on the device
         if raw:
             from .transforms import target_size
@@ -396,9 +480,9 @@ class Detector:
         handles = [self._handle(H, W, k) for k in range(ns)]
         chunk = max(bb, (chunk // bb) * bb)
         rows = torch.empty(N, Q, 16, device=dev, dtype=torch.float32)
-        if getattr(self, "_pinned", None) is None or self._pinned.shape[0] < N:
+        if _pack is None and (getattr(self, "_pinned", None) is None or self._pinned.shape[0] < N):
             self._pinned = torch.empty(N, Q, 16, dtype=torch.float32, pin_memory=True)
-        host = self._pinned[:N]
+        host = self._pinned[:N] if _pack is None else None
         if getattr(self, "_streams", None) is None or len(self._streams) != ns:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(ns)]
             mk = lambda n: torch.empty(mb, Q, n, device=dev, dtype=torch.float32)
@@ -456,6 +540,10 @@ class Detector:
                                                        K9.ctypes.data_as(_lib.c_float_p), ctypes.c_float(img_w),
                                                        ctypes.c_float(img_h), _lib.ptr(rows[b0:b0 + B]), sp),
                                "odam_detr_postprocess")
+                    if _pack is not None:
+                        self.select_pack(rows[b0:b0 + B], _pack["frame_ids"][b0:b0 + B], _pack["seq_size"], _pack["threshold"],
+                                         _pack["nms_2d"], out=(_pack["out"][0][b0:b0 + B], _pack["out"][1][b0:b0 + B]),
+                                         stream=self._streams[k].cuda_stream)
                     if on_host:
                         stage_free[k][j] = torch.cuda.Event()
                         stage_free[k][j].record(self._streams[k])
@@ -463,6 +551,8 @@ class Detector:
                     e = torch.cuda.Event()
                     e.record(self._streams[k])
                     main.wait_event(e)
+                if _pack is not None:        # the caller's stream is ordered behind every batch; nothing goes to the host
+                    continue
                 host[c0:c1].copy_(rows[c0:c1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(main)

@@ -133,9 +133,14 @@ def allgather_detections(blk, cnt, n_frames, device=None, force=False):
     blocks of the whole scene in frame order on every rank.  One message per rank: the block and its per-frame counts
     travel in ONE float32 tensor [F_pad, 30 * 15 + 1] (the count in the last column; exact, it is <= 30) -- one upload,
     one all_gather_into_tensor, one download.  `force`: run the collective even in a world of one (exercises the RCCL
-    call path on a single GPU)."""
+    call path on a single GPU).  `blk`, `cnt` may be torch tensors (OdamProcess.detect_frames_packed): tensors on the
+    collective's own device go into it as they are -- no host staging, no upload -- on the native and the RCCL path; what is
+    returned is the same numpy pair either way."""
     rank, ws = world()
+    tensors = torch.is_tensor(blk)
     if ws == 1 and not (force and dist.is_available() and dist.is_initialized()):
+        if tensors:
+            return blk.cpu().numpy(), cnt.cpu().numpy()
         return blk, cnt
     dev = device or ("cuda" if (dist.get_backend() == "nccl" or _NATIVE) else "cpu")
     per = -(-n_frames // ws)  # padded shard length so all_gather_into_tensor sees equal shapes
@@ -143,13 +148,21 @@ def allgather_detections(blk, cnt, n_frames, device=None, force=False):
     nat = _native(dev)
     if nat is not None:
         dev = nat[3]
+    resident = tensors and blk.is_cuda and torch.device(dev).type == "cuda"
+    if tensors and not resident:      # host tensors, or a host collective (gloo): the numpy path below
+        blk, cnt = blk.cpu().numpy(), cnt.cpu().numpy()
     if nat is not None:      # the library's own collective (include/odam_comm.h, odam_allgather_detections): block and counts stay separate
         import ctypes
         from . import _lib
-        hb = np.full((per, MAX_DETS, DET_COLS), -1.0, np.float32)
-        hc = np.zeros(per, np.int32)
-        hb[:len(cnt)] = blk; hc[:len(cnt)] = cnt
-        db, dc = torch.from_numpy(hb).to(dev), torch.from_numpy(hc).to(dev)
+        if resident:
+            db = torch.full((per, MAX_DETS, DET_COLS), -1.0, dtype=torch.float32, device=dev)
+            dc = torch.zeros(per, dtype=torch.int32, device=dev)
+            db[:len(cnt)] = blk; dc[:len(cnt)] = cnt
+        else:
+            hb = np.full((per, MAX_DETS, DET_COLS), -1.0, np.float32)
+            hc = np.zeros(per, np.int32)
+            hb[:len(cnt)] = blk; hc[:len(cnt)] = cnt
+            db, dc = torch.from_numpy(hb).to(dev), torch.from_numpy(hc).to(dev)
         ab = torch.empty((ws, per, MAX_DETS, DET_COLS), dtype=torch.float32, device=dev)
         ac = torch.empty((ws, per), dtype=torch.int32, device=dev)
         with torch.cuda.device(torch.device(dev)):
@@ -162,11 +175,17 @@ def allgather_detections(blk, cnt, n_frames, device=None, force=False):
             s, e = frame_shard(n_frames, r, ws)
             ob.append(gb[r, :e - s]); oc.append(gc[r, :e - s])
         return np.concatenate(ob), np.concatenate(oc)
-    host = np.full((per, W + 1), -1.0, np.float32)
-    host[:, W] = 0.0
-    host[:len(cnt), :W] = blk.reshape(len(cnt), W)
-    host[:len(cnt), W] = cnt
-    mine = torch.from_numpy(host).to(dev)
+    if resident:
+        mine = torch.full((per, W + 1), -1.0, dtype=torch.float32, device=dev)
+        mine[:, W] = 0.0
+        mine[:len(cnt), :W] = blk.reshape(len(cnt), W)
+        mine[:len(cnt), W] = cnt
+    else:
+        host = np.full((per, W + 1), -1.0, np.float32)
+        host[:, W] = 0.0
+        host[:len(cnt), :W] = blk.reshape(len(cnt), W)
+        host[:len(cnt), W] = cnt
+        mine = torch.from_numpy(host).to(dev)
     allr = torch.empty((ws * per, W + 1), dtype=torch.float32, device=dev)
     dist.all_gather_into_tensor(allr, mine)
     g = allr.cpu().numpy()

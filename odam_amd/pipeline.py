@@ -32,13 +32,18 @@ def _f64_words(a):
     return np.ascontiguousarray(a, np.float64).reshape(len(a), 24).view(np.float32)
 
 
-def detect_gathered(detect, first, end, device=None, force=False):
+def detect_gathered(detect, first, end, device=None, force=False, packed=False):
     """Frames first .. end-1 of the scene: this rank detects its contiguous share (parallel.frame_shard of the span), the
     blocks are all-gathered, every rank returns the rows of ALL frames of the span in frame order (list of [n, 79] float64).
-    `detect(f0, f1)` -> list (per frame) of [n, 79] rows for scene frames f0 .. f1-1."""
+    `detect(f0, f1)` -> list (per frame) of [n, 79] rows for scene frames f0 .. f1-1; with `packed`, the packed block and
+    counts themselves (OdamProcess.detect_frames_packed: device tensors that go straight into the gather)."""
     rank, ws = parallel.world()
     n = end - first
     s, e = parallel.frame_shard(n, rank, ws)
+    if packed and e > s:
+        blk, cnt = detect(first + s, first + e)
+        blk, cnt = parallel.allgather_detections(blk, cnt, n, device, force=force)
+        return parallel.unpack_detections(blk, cnt)
     rows = detect(first + s, first + e) if e > s else []
     blk, cnt = parallel.pack_detections(rows)
     blk, cnt = parallel.allgather_detections(blk, cnt, n, device, force=force)
@@ -88,7 +93,8 @@ def _associate(proc, frame_ids, T_wcs, c0, rows):
             proc.process_frame(None, int(frame_ids[c0 + i]), T_wcs[c0 + i], detections=r)
 
 
-def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=0, device=None, force=False, stages=None, overlap=None):
+def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=0, device=None, force=False, stages=None, overlap=None,
+              device_select=False):
     """The driver loop of run_processor.py:70-83 for one scene on the ranks of the current process group.
 
     proc      OdamProcess after init_sequence (its detector is used unless `detect` is given; its associator and fitter always)
@@ -103,16 +109,22 @@ def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=
               sum; on ONE GPU the association's short launches wait behind the detector's queued ones (profiles/
               r4_experiments_not_kept.txt #12, #13) and the overlap returns nothing.  Only the worker issues collectives while it
               runs, in chunk order on every rank; results are identical with and without (the same calls on the same data).
+    device_select  with the default `detect` only: a rank's share goes through proc.detect_frames_packed -- threshold, NMS and the rows
+              on the device -- and the packed block straight into the gather; the same detections, bit for bit.  Frames of one size.
     Returns the second optim_process dict (what the reference pickles), identical on every rank; proc.tracks holds the
     unmerged tracks."""
     import sys
     import time
+    packed = bool(device_select) and detect is None
     if detect is None:
         if frames is None:
             raise ValueError("run_scene: give `frames` or a `detect` callable")
 
         def detect(f0, f1):
             return [np.asarray(r, np.float64).reshape(-1, 79) for r in proc.detect_frames(list(frames[f0:f1]), list(frame_ids[f0:f1]))]
+        if packed:
+            def detect(f0, f1):      # noqa: F811
+                return proc.detect_frames_packed(list(frames[f0:f1]), list(frame_ids[f0:f1]))
     t = {"detect_gather": 0.0, "associate": 0.0}
     spans = parallel.chunk_spans(n_frames, chunk or n_frames)
     if overlap is None:
@@ -148,7 +160,7 @@ def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=
                     if cancel.is_set():      # the consumer failed: issue no further collective from this rank
                         return
                     s0 = time.perf_counter()
-                    rows = detect_gathered(detect, c0, c1, device, force)
+                    rows = detect_gathered(detect, c0, c1, device, force, packed)
                     if not put((c0, rows, time.perf_counter() - s0)):
                         return
                 put(None)
@@ -188,7 +200,7 @@ def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=
     else:
         for c0, c1 in spans:
             s0 = time.perf_counter()
-            rows = detect_gathered(detect, c0, c1, device, force)
+            rows = detect_gathered(detect, c0, c1, device, force, packed)
             s1 = time.perf_counter()
             _associate(proc, frame_ids, T_wcs, c0, rows)
             t["detect_gather"] += s1 - s0

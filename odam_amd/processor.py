@@ -208,6 +208,37 @@ class OdamProcess:
     def run_detector(self, rgb, frame_id, T_wc):
         return self.detect_frames([rgb], [frame_id])[0]
 
+    def detect_frames_packed(self, rgbs, frame_ids):
+        """detect_frames with threshold, NMS and the rows on the device (Detector.select_pack): returns device tensors
+        (block float32 [N,30,15], count int32 [N]) equal, bit for bit, to parallel.pack_detections(self.detect_frames(rgbs,
+        frame_ids)) -- what the all-gather of the sharded chain sends -- without the [N,Q,16] rows coming to the host.
+        For frames of ONE size only: a mixed-size list raises ValueError and keeps using detect_frames (its padded batches are
+        post-processed frame by frame, each with its own size)."""
+        size_of = lambda rgb: tuple(rgb.size) if hasattr(rgb, "size") and not isinstance(rgb, np.ndarray) else rgb.shape[1::-1]
+        sizes = {size_of(rgb) for rgb in rgbs}
+        if len(sizes) > 1:
+            raise ValueError(f"detect_frames_packed: frames of one size only, got {sorted(sizes)}; use detect_frames")
+        det = self.detector
+        N = len(rgbs)
+        blk = torch.empty(N, 30, 15, device=det.device, dtype=torch.float32)
+        cnt = torch.empty(N, device=det.device, dtype=torch.int32)
+        mb = getattr(det, "max_batch", 1)
+        on_device = getattr(self.transforms, "on_device", False)
+        if on_device:
+            det.resize = (self.transforms.size, self.transforms.max_size)
+        m = self.sequence_meta
+        for b0 in range(0, N, mb):
+            chunk = rgbs[b0:b0 + mb]
+            if on_device:   # raw uint8 frames up, transform + forward on the GPU
+                raw = np.stack([np.asarray(rgb, np.uint8) for rgb in chunk])
+                pred = det.forward_u8(torch.from_numpy(raw).to(det.device))
+            else:
+                pred = det(torch.stack([self.transforms(rgb, None)[0] for rgb in chunk]))
+            rows = det.postprocess_rows(pred, next(iter(sizes)), m.K, on_device=True)
+            det.select_pack(rows, frame_ids[b0:b0 + len(chunk)], (m.img_w, m.img_h), float(self.detect_threshold),
+                            out=(blk[b0:b0 + len(chunk)], cnt[b0:b0 + len(chunk)]))
+        return blk, cnt
+
     # ---- tracks (processor.py:95-257) --------------------------------------------------------------
     def _img_size_row(self):
         m = self.sequence_meta
