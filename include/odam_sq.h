@@ -72,6 +72,45 @@ int odam_sq_fit_batch(odam_sq_ctx* ctx, int n_obj, const float* init_params, con
                       float* out_params, float* out_points, float* loss_log, float* traj,
                       void* stream);
 
+/*
+ * The resumable fit.  odam_sq_fit_batch loses the Adam moments, the step count and the scales the prior is measured from when its
+ * launch ends; this entry point takes and returns them, so that a fit of n steps equals a fit of k steps followed by a resumed fit
+ * of n - k steps on the same views, bit for bit, on every output.  Arguments as odam_sq_fit_batch, and:
+ *   state_in   [dev]  [n_obj][ODAM_SQ_STATE_FLOATS]  nullable.  Null: a cold start from init_params, exactly as odam_sq_fit_batch.
+ *                     Given: EVERY object starts from its row and init_params is ignored (may be null).  An object that starts
+ *                     cold inside such a call gets the row of a fit that has not begun: its initial parameters, zero moments,
+ *                     scales_init = its initial scales, 0 steps.
+ *   t0         [host] [n_obj]  steps each object has taken so far = word 30 of its row, as the caller knows it on the host.
+ *                     Required with state_in, ignored without.  All checks are made on it before anything is enqueued, so neither
+ *                     path reads the device back: a negative entry is ODAM_E_INVALID; t0[i] + n_iters > max_iters of the context
+ *                     is ODAM_E_LIMIT with both numbers in the message.  (The kernel takes the count from the row and clamps it to
+ *                     the table; a row that disagrees with t0 is the caller's error and gives a defined, wrong, result.)
+ *   state_out  [dev]  [n_obj][ODAM_SQ_STATE_FLOATS]  nullable; may be the buffer of state_in (a workgroup reads its row before the
+ *                     first step, one stores it after the last; but not where the view split is taken -- several workgroups read).
+ * State row (float32 words):
+ *    0 ..  8  parameters (= out_params)
+ *    9 .. 17  Adam first moments  (exp_avg)
+ *   18 .. 26  Adam second moments (exp_avg_sq)
+ *   27 .. 29  scales_init: the scales of the FIRST launch's init_params, which the scale prior is measured from (sq_libs.py:454,465)
+ *   30        steps taken so far, an exact small integer
+ *   31        representation code of the launch that wrote the row (checked by the caller: odam_amd/sq.py refuses a mismatch)
+ * Step i of the launch uses row t0 + i of the bias-correction table odam_sq_create uploaded.  loss_log and traj hold this launch's
+ * n_iters rows only.  class_id is passed again with every call: an object without prior (class_id < 0) resumes as it started.
+ * Scheduling (view split, two workgroups per CU, longest object first) is that of odam_sq_fit_batch for the same views; with several
+ * workgroups per object all of them load the row and the one that writes out_params stores it.
+ */
+#define ODAM_SQ_STATE_FLOATS 32
+int odam_sq_fit_resume(odam_sq_ctx* ctx, int n_obj, const float* init_params, const int* class_id,
+                       const int* view_offsets, const float* P, const float* tgt, const float* mask,
+                       const float* prior_icov, int n_iters, int representation, int max_views,
+                       float* out_params, float* out_points, float* loss_log, float* traj,
+                       const float* state_in, const int* t0, float* state_out, void* stream);
+
+/* Shape of the newest fit launch of this context (host-side note, no device work): shape4 [host][4] = workgroups in the grid, threads
+ * per workgroup (1024, or 512 for two workgroups per CU), workgroups per object of the view split (1 = off), 1 if the objects were
+ * dealt longest first. */
+int odam_sq_last_launch(odam_sq_ctx* ctx, int* shape4);
+
 /* Surface points of n super-quadrics: params [dev][n][9] -> out_points [dev][n][1000][3]. */
 int odam_sq_points_batch(odam_sq_ctx* ctx, int n, const float* params, float* out_points, void* stream);
 

@@ -86,6 +86,10 @@ struct FitArgs {
     int force_lanes_per_view;         // 0 = choose (experiments: ODAM_SQ_S)
     unsigned split_wait_ticks;        // bounded wait for a partner's rows, 100 MHz wall clock (30 us: > one slice of phase E)
     const int* order;                 // launches of more workgroups than CUs (no view split): workgroup b fits object order[b] -- longest first; or null
+    // resumable fits (odam_sq_fit_resume; read by the ST instantiations only): rows of ODAM_SQ_STATE_FLOATS floats, see include/odam_sq.h
+    const float* state_in;            // [n_obj][32] or null (cold start from init_params)
+    float* state_out;                 // [n_obj][32] or null
+    int max_t0;                       // max_iters - n_iters: the largest first table row a state may ask for (validated on the host; clamped here)
 };
 
 struct Lds {
@@ -197,7 +201,9 @@ __device__ inline void merge_max(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
 
-template <int NT>      // 1024: sixteen waves, one workgroup per CU; 512: eight waves at <= 128 registers, two workgroups per CU (launch_fit decides)
+// ST: the resumable form (odam_sq_fit_resume).  It starts from a state row where one is given, indexes the Adam table from the row's step
+// count and stores the row of the fit's end; odam_sq_fit_batch launches the ST = false instantiation, which holds none of that.
+template <int NT, bool ST = false>      // 1024: sixteen waves, one workgroup per CU; 512: eight waves at <= 128 registers, two workgroups per CU (launch_fit decides)
 __global__ __launch_bounds__(NT, 4) void sq_fit_kernel(FitArgs A) {      // (second argument: waves per SIMD -- 128 registers either way)
     extern __shared__ __align__(16) float smem[];
     const int tid = threadIdx.x;
@@ -242,13 +248,33 @@ __global__ __launch_bounds__(NT, 4) void sq_fit_kernel(FitArgs A) {      // (sec
     const bool lead = (wj == 0);                    // writes the object's outputs
     unsigned absent = 0;                              // bit jj: partner jj missed a deadline once -> no more waiting for it
 
-    if (tid < 9) {
-        L.p[tid] = A.init_params[(size_t)obj * 9 + tid];
-        L.m[tid] = 0.0f;
-        L.v[tid] = 0.0f;
-        if (use_prior) L.icov[tid] = A.prior_icov[cls * 9 + tid];
+    // every workgroup of a split object loads the same state row and keeps it in lock step like the parameters; t0 = steps taken so far
+    int t0 = 0;
+    const float* st_in = nullptr;
+    if constexpr (ST) {
+        if (A.state_in) {
+            st_in = A.state_in + (size_t)obj * ODAM_SQ_STATE_FLOATS;
+            t0 = (int)st_in[30];
+            t0 = t0 < 0 ? 0 : (t0 > A.max_t0 ? A.max_t0 : t0);      // (the host refused anything outside: never past the table)
+        }
     }
-    if (tid < 3) L.s0[tid] = A.init_params[(size_t)obj * 9 + 4 + tid];
+    if (ST && st_in) {
+        if (tid < 9) {
+            L.p[tid] = st_in[tid];
+            L.m[tid] = st_in[9 + tid];
+            L.v[tid] = st_in[18 + tid];
+            if (use_prior) L.icov[tid] = A.prior_icov[cls * 9 + tid];
+        }
+        if (tid < 3) L.s0[tid] = st_in[27 + tid];      // the prior is measured from the scales the FIRST launch started at
+    } else {
+        if (tid < 9) {
+            L.p[tid] = A.init_params[(size_t)obj * 9 + tid];
+            L.m[tid] = 0.0f;
+            L.v[tid] = 0.0f;
+            if (use_prior) L.icov[tid] = A.prior_icov[cls * 9 + tid];
+        }
+        if (tid < 3) L.s0[tid] = A.init_params[(size_t)obj * 9 + 4 + tid];
+    }
     __syncthreads();
 
     int Pn = 1;
@@ -848,7 +874,7 @@ __global__ __launch_bounds__(NT, 4) void sq_fit_kernel(FitArgs A) {      // (sec
                 g += gs[tid - 4];
             }
             if (tid < n_opt) {
-                const float* tab = A.adam_tab + 4 * it;
+                const float* tab = A.adam_tab + 4 * (ST ? t0 + it : it);
                 float pp = L.p[tid], mm = L.m[tid], vv = L.v[tid];
                 adam_scalar(pp, mm, vv, g, (tid < 7) ? tab[0] : tab[1], tab[2]);
                 L.p[tid] = pp; L.m[tid] = mm; L.v[tid] = vv;
@@ -868,6 +894,14 @@ __global__ __launch_bounds__(NT, 4) void sq_fit_kernel(FitArgs A) {      // (sec
         for (int k = 0; k < 8; k++) A.out_points[k] = (float)st_acc[k];
 #endif
     if (A.out_params && tid < 9 && lead) A.out_params[(size_t)obj * 9 + tid] = L.p[tid];
+    if constexpr (ST) {
+        if (A.state_out && lead) {      // the lanes that own the values in phase F; the workgroup that writes out_params
+            float* so = A.state_out + (size_t)obj * ODAM_SQ_STATE_FLOATS;
+            if (tid < 9) { so[tid] = L.p[tid]; so[9 + tid] = L.m[tid]; so[18 + tid] = L.v[tid]; }
+            if (tid < 3) so[27 + tid] = L.s0[tid];
+            if (tid == 0) { so[30] = (float)(t0 + A.n_iters); so[31] = (float)A.representation; }
+        }
+    }
 }
 
 }  // namespace
@@ -895,6 +929,7 @@ struct odam_sq_ctx {
     int* d_order = nullptr;
     int* h_order = nullptr;       // pinned staging of the same size (the upload is stream-ordered: no NULL-stream copy that would wait for other streams)
     size_t order_n = 0;
+    int last_grid = 0, last_threads = 0, last_split = 0, last_ordered = 0;      // shape of the newest fit launch (odam_sq_last_launch)
     odam_dq_state dq;             // the dual-quadric fit's own Adam table (dq_fit.hip); nothing of the fields above is shared with it
 };
 
@@ -940,6 +975,8 @@ extern "C" int odam_sq_create(int max_iters, odam_sq_ctx** out) {
         ODAM_HIP(hipMemcpy(c->d_adam, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
         ODAM_HIP(hipFuncSetAttribute((const void*)sq_fit_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ODAM_HIP(hipFuncSetAttribute((const void*)sq_fit_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ODAM_HIP(hipFuncSetAttribute((const void*)sq_fit_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ODAM_HIP(hipFuncSetAttribute((const void*)sq_fit_kernel<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         return ODAM_OK;
     }();
     if (rc != ODAM_OK) {
@@ -974,7 +1011,7 @@ extern "C" int odam_sq_destroy(odam_sq_ctx* c) {
     return ODAM_OK;
 }
 
-static int launch_fit(odam_sq_ctx* ctx, int n_obj, FitArgs& A, int max_views, hipStream_t stream) {
+static int launch_fit(odam_sq_ctx* ctx, int n_obj, FitArgs& A, int max_views, hipStream_t stream, bool resumable = false) {
     int pn = 1;
     while (pn < max_views) pn <<= 1;
     A.draws = ctx->d_draws;
@@ -1066,7 +1103,11 @@ static int launch_fit(odam_sq_ctx* ctx, int n_obj, FitArgs& A, int max_views, hi
         }
     }
     const bool two = NT_MAX == 1024 && uniform && 2 * bytes <= 160 * 1024;
-    if (two) hipLaunchKernelGGL(sq_fit_kernel<512>, dim3(grid), dim3(512), bytes, stream, A);
+    ctx->last_grid = grid; ctx->last_threads = two ? 512 : NT_MAX; ctx->last_split = A.split; ctx->last_ordered = A.order != nullptr;
+    if (resumable) {      // same grid, same workgroup size, same order: a resumed launch is scheduled exactly as a cold one
+        if (two) hipLaunchKernelGGL((sq_fit_kernel<512, true>), dim3(grid), dim3(512), bytes, stream, A);
+        else hipLaunchKernelGGL((sq_fit_kernel<NT_MAX, true>), dim3(grid), dim3(NT_MAX), bytes, stream, A);
+    } else if (two) hipLaunchKernelGGL(sq_fit_kernel<512>, dim3(grid), dim3(512), bytes, stream, A);
     else hipLaunchKernelGGL(sq_fit_kernel<NT_MAX>, dim3(grid), dim3(NT_MAX), bytes, stream, A);
     ODAM_HIP(hipGetLastError());
     return ODAM_OK;
@@ -1091,6 +1132,50 @@ extern "C" int odam_sq_fit_batch(odam_sq_ctx* ctx, int n_obj, const float* init_
     A.n_iters = n_iters; A.representation = representation;
     A.out_params = out_params; A.out_points = out_points; A.loss_log = loss_log; A.traj = traj;
     return launch_fit(ctx, n_obj, A, max_views, (hipStream_t)stream);
+}
+
+// The resumable fit: the launch of odam_sq_fit_batch on the ST instantiation of the kernel.  Everything that can refuse the call is decided
+// here from host values (the caller's t0 array): no read-back of the state, nothing enqueued before the checks are through.
+extern "C" int odam_sq_fit_resume(odam_sq_ctx* ctx, int n_obj, const float* init_params, const int* class_id,
+                                  const int* view_offsets, const float* P, const float* tgt,
+                                  const float* mask, const float* prior_icov, int n_iters,
+                                  int representation, int max_views, float* out_params, float* out_points,
+                                  float* loss_log, float* traj, const float* state_in, const int* t0,
+                                  float* state_out, void* stream) {
+    if (!ctx || (!init_params && !state_in) || !view_offsets || !P || !tgt || !mask || !out_params)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_fit_resume: null pointer");
+    if (state_in && !t0) return odam_fail(ODAM_E_INVALID, "odam_sq_fit_resume: state_in without the host array t0");
+    if (n_obj < 0 || n_iters < 0 || representation < 0 || representation > 2)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_fit_resume: bad size / representation");
+    if (n_iters > ctx->max_iters) {
+        std::snprintf(g_odam_err, sizeof(g_odam_err), "odam_sq_fit_resume: n_iters %d > max_iters %d of the context", n_iters, ctx->max_iters);
+        return ODAM_E_LIMIT;
+    }
+    if (state_in)
+        for (int i = 0; i < n_obj; i++) {
+            if (t0[i] < 0) return odam_fail(ODAM_E_INVALID, "odam_sq_fit_resume: negative step count in t0");
+            if (t0[i] > ctx->max_iters - n_iters) {
+                std::snprintf(g_odam_err, sizeof(g_odam_err), "odam_sq_fit_resume: object %d has taken %d steps, %d more make %d > max_iters %d "
+                              "of the context", i, t0[i], n_iters, t0[i] + n_iters, ctx->max_iters);
+                return ODAM_E_LIMIT;
+            }
+        }
+    if (max_views < 1 || max_views > 16 * ODAM_SQ_MAX_VIEWS)
+        return odam_fail(ODAM_E_LIMIT, "odam_sq_fit_resume: max_views outside 1..16 * ODAM_SQ_MAX_VIEWS");
+    if (n_obj == 0) return ODAM_OK;
+    FitArgs A{};
+    A.init_params = init_params; A.class_id = class_id; A.view_offsets = view_offsets;
+    A.P = P; A.tgt = tgt; A.mask = mask; A.prior_icov = prior_icov;
+    A.n_iters = n_iters; A.representation = representation;
+    A.out_params = out_params; A.out_points = out_points; A.loss_log = loss_log; A.traj = traj;
+    A.state_in = state_in; A.state_out = state_out; A.max_t0 = ctx->max_iters - n_iters;
+    return launch_fit(ctx, n_obj, A, max_views, (hipStream_t)stream, true);
+}
+
+extern "C" int odam_sq_last_launch(odam_sq_ctx* ctx, int* shape4) {
+    if (!ctx || !shape4) return odam_fail(ODAM_E_INVALID, "odam_sq_last_launch: null pointer");
+    shape4[0] = ctx->last_grid; shape4[1] = ctx->last_threads; shape4[2] = ctx->last_split; shape4[3] = ctx->last_ordered;
+    return ODAM_OK;
 }
 
 extern "C" int odam_sq_points_batch(odam_sq_ctx* ctx, int n, const float* params, float* out_points,

@@ -284,11 +284,36 @@ def _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, 
     return out_dict
 
 
+def _check_resume(resume, representation, n_objs):
+    """the refusals of optim_process(resume=...), before any work: -> (state rows, track indices) or (None, None)"""
+    if representation == "dual_quadric":
+        raise ValueError('resume / return_state: the "dual_quadric" fit is not resumable (super_quadric, cube and quadric are)')
+    if resume is None:
+        return None, None
+    if resume["representation"] != representation:
+        raise ValueError(f"resume holds the state of a {resume['representation']!r} fit, this call fits {representation!r}")
+    ids = np.asarray(resume["track_ids"], np.int64).reshape(-1)
+    if len(ids) and (ids.min() < 0 or ids.max() >= n_objs):
+        raise ValueError(f"resume refers to track {int(ids.max() if ids.max() >= n_objs else ids.min())}, the list has {n_objs} tracks "
+                         "(state is keyed by track index: it does not survive merge_process)")
+    if len(resume["state"]) != len(ids):
+        raise ValueError(f"resume: {len(resume['state'])} state rows for {len(ids)} track indices")
+    return resume["state"], ids
+
+
 def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representation, prior, n_iters, n_views,
-                  fitter=None, return_params=False):
-    """run_multi_view.py:22-76 with the per-object fits batched on the GPU."""
+                  fitter=None, return_params=False, resume=None, return_state=False):
+    """run_multi_view.py:22-76 with the per-object fits batched on the GPU.
+
+    Resumable (SqFitter.fit's state): with return_state the dict also holds "state" = {"state": [k, 32] rows, "track_ids": the k
+    tracks fitted, "representation"}; passed back as `resume`, every track in it that is fitted again continues from its row for
+    n_iters MORE steps on its current views (the constraint rows are rebuilt from the track as always), every other track starts
+    cold.  State is keyed by track index: valid while association only appends tracks, invalid after merge_process."""
     fitter = fitter or default_fitter()
     n_objs = len(tracks)
+    res_state = res_ids = None
+    if resume is not None or return_state:
+        res_state, res_ids = _check_resume(resume, representation, n_objs)
     if _UniqueFrames.applies(img_names):
         frame_to_img = _UniqueFrames(img_names)
     else:
@@ -331,10 +356,24 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
         return _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, fit_mask, n_iters, fitter, return_params)
     params = {i: inits[i] for i in range(n_objs)}
     points = {}
+    state_out = None
     if fit_ids:
+        more = {}
+        if resume is not None or return_state:
+            import torch
+            st = torch.from_numpy(_sq.cold_state(np.stack([inits[i] for i in fit_ids]), representation))
+            if res_ids is not None and len(res_ids):
+                row_of = {int(t): j for j, t in enumerate(res_ids)}
+                dst = [j for j, i in enumerate(fit_ids) if i in row_of]
+                if dst:      # these continue; the rest of st stays the row of a fit that has not begun
+                    rs = res_state if torch.is_tensor(res_state) else torch.as_tensor(np.asarray(res_state, np.float32))
+                    st = st.to(rs.device)
+                    st[torch.as_tensor(dst, device=rs.device)] = rs[torch.as_tensor([row_of[fit_ids[j]] for j in dst], device=rs.device)].to(torch.float32)
+            more = dict(state=st, want_state=bool(return_state))
         out = fitter.fit(np.stack([inits[i] for i in fit_ids]), [classes[i] for i in fit_ids], fit_counts,
                          np.concatenate(fit_P), np.concatenate(fit_tgt), np.concatenate(fit_mask),
-                         n_iters=n_iters, representation=representation, prior=bool(prior), want_points=True)
+                         n_iters=n_iters, representation=representation, prior=bool(prior), want_points=True, **more)
+        state_out = out.get("state") if return_state else None
         fp = out["params"].cpu().numpy()
         fpts = out["points"].cpu().numpy()
         for j, i in enumerate(fit_ids):
@@ -357,4 +396,7 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
     if return_params:
         out_dict["params"] = np.stack([params[i] for i in range(n_objs)]) if n_objs else np.zeros((0, 9), np.float32)
         out_dict["fitted"] = np.array([i in points for i in range(n_objs)], bool)
+    if return_state:
+        out_dict["state"] = {"state": state_out if state_out is not None else np.zeros((0, _sq.STATE_FLOATS), np.float32),
+                             "track_ids": np.asarray(fit_ids, np.int64), "representation": representation}
     return out_dict

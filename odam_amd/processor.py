@@ -104,6 +104,8 @@ class OdamProcess:
         self._exposed = True        # somebody may hold (and edit) the list self.tracks returned: the mirror is re-checked before the next fast frame
         self.sequence_meta = None
         self.fitter = fitter
+        self.refine_fitter = None   # refine(): its own context, with a bias-correction table long enough for a whole scan (REFINE_MAX_ITERS)
+        self._refine_state = None   # refine(): what multi_view.optim_process(return_state=True) returned last, keyed by track index
         self.logger = logging.getLogger('OdamProcess')
 
     # `tracks` is the reference's attribute (src/processor.py:300; a list of [n, 82] arrays, index = track id).  The fast path of
@@ -165,6 +167,7 @@ class OdamProcess:
         self._sum_cache = []
         self._win_checked = None
         self._frame_token = None
+        self._refine_state = None
         if getattr(self, "_win", None) is not None:
             self._win.reset()
 
@@ -635,7 +638,33 @@ class OdamProcess:
     # ---- back end (processor.py:347-368) -----------------------------------------------------------
     def merge_process(self, data):
         self.logger.info("Merging tracks")
+        if self._refine_state is not None:      # keyed by track index, and merging renumbers the tracks
+            self.logger.info("Dropping the fit state of %d refined tracks: track indices change in merge_process",
+                             len(self._refine_state["track_ids"]))
+            self._refine_state = None
         return merge.merge_process(data, self.usable_frames)
+
+    REFINE_MAX_ITERS = 4000     # steps one track can take over all refine() calls of a sequence (rows of the context's Adam table)
+
+    def refine(self, n_iters=50, return_params=False):
+        """The online call: current shapes of the live tracks while the scan is running.  Fits every track with enough views for
+        n_iters steps, CONTINUING every track an earlier refine() of this sequence fitted (parameters, Adam moments, step count and
+        the scales the prior is measured from are kept here, per track index) on the views it has now; a new track, or one that had
+        too few views last time, starts cold.  Returns optim_process's dict.  Reads the tracks and nothing else: association, and
+        optim_process at the end of the scan, go on as if it had never been called.  init_sequence clears the state, merge_process
+        drops it (track indices change there).  Not for representation "dual_quadric"."""
+        if self.representation == "dual_quadric":
+            raise ValueError('refine: the "dual_quadric" fit is not resumable')
+        if self.refine_fitter is None:
+            self.refine_fitter = multi_view._sq.SqFitter(str(getattr(self.detector, "device", "cuda:0")), self.REFINE_MAX_ITERS)
+        m = self.sequence_meta
+        out = multi_view.optim_process(self.tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
+                                       self.representation, prior=True, n_iters=int(n_iters), n_views=10,
+                                       fitter=self.refine_fitter, return_params=return_params,
+                                       resume=self._refine_state, return_state=True)
+        # (a track fitted once is fitted every time after: its views only grow, so the new rows cover the old ones)
+        self._refine_state = out.pop("state")
+        return out
 
     def optim_process(self, tracks, return_params=False):
         m = self.sequence_meta

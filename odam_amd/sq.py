@@ -20,6 +20,7 @@ WG_VIEWS = 1024          # rows one workgroup reduces (ODAM_SQ_MAX_VIEWS)
 MAX_VIEWS = 16 * WG_VIEWS  # per object: split over up to 16 workgroups
 NAMES = ("x_min", "x_max", "y_min", "y_max")  # sq_libs.py:438
 REPRESENTATIONS = {"super_quadric": 0, "cube": 1, "quadric": 2, "dual_quadric": 3}   # 0..2: odam_sq_fit_batch codes; 3: fit_dual
+STATE_FLOATS = 32        # ODAM_SQ_STATE_FLOATS: parameters 0..8, exp_avg 9..17, exp_avg_sq 18..26, scales_init 27..29, steps 30, representation 31
 DQ_POINTS = 2500         # 50 x 50 angle grid of DualQuadric.compute_ellipsoid_points (sq_libs.py:325)
 # sq_libs.py:13-22
 CLASS_MAPPER = {0: "03211117", 1: "04379243", 2: "02808440", 3: "02747177",
@@ -65,6 +66,27 @@ def init_params(translate, angle, dims, representation="super_quadric"):
                            shapes]).astype(np.float32)
 
 
+# odam_sq_fit_resume as include/odam_sq.h declares it (tests/test_sq_resume_host.py holds the two together)
+FIT_RESUME_ARGTYPES = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 8)
+
+
+def _fit_resume_entry():
+    f = _lib.lib().odam_sq_fit_resume
+    if f.argtypes is None:
+        f.argtypes, f.restype = FIT_RESUME_ARGTYPES, ctypes.c_int
+    return f
+
+
+def cold_state(params0, representation):
+    """[n, 32] float32 rows of fits that have not begun (include/odam_sq.h): what a track that starts cold gets inside a resumed call"""
+    p = np.asarray(params0, np.float32).reshape(-1, 9)
+    st = np.zeros((len(p), STATE_FLOATS), np.float32)
+    st[:, 0:9] = p
+    st[:, 27:30] = p[:, 4:7]
+    st[:, 31] = REPRESENTATIONS[representation]
+    return st
+
+
 class SqFitter:
     """Owns the device context (constant sampler draws + Adam tables)."""
 
@@ -102,7 +124,7 @@ class SqFitter:
         return self._prior
 
     def fit(self, params0, class_ids, view_counts, P, tgt, mask, n_iters=200, representation="super_quadric",
-            prior=True, want_points=True, want_loss=False, want_traj=False):
+            prior=True, want_points=True, want_loss=False, want_traj=False, state=None, want_state=False):
         """Batched SuperQuadricOptimizer.run.
 
         params0 [n,9] f32; class_ids [n] int; view_counts [n] int; P [sumF,3,4]/[sumF,12] f32;
@@ -111,16 +133,54 @@ class SqFitter:
         Objects with more than 1024 views need the library's view split (k workgroups per object, k x padded object
         count <= number of CUs): they are fitted in groups small enough for that; fits are independent, so the
         grouping does not change any result.
+
+        Resumable fits (odam_sq_fit_resume): with want_state the dict also holds "state", a device tensor [n, 32] (layout in
+        include/odam_sq.h); passed back as `state` (host or device, numpy or torch) the fit continues where that one stopped --
+        params0 is then ignored, the views may have changed, loss / traj hold the new steps only -- and k steps followed by n - k
+        resumed steps on the same views are the bits of n steps.  The steps taken so far and the representation are read from the
+        state (a small copy to the host for a device tensor); more than max_iters steps in all, or a state of another
+        representation, is refused before anything is launched.  Without either argument this is the call it always was.
         """
         vc = np.asarray(view_counts, np.int64)
+        resumable = state is not None or want_state
+        st = t0 = None
+        if state is not None:
+            st, t0 = self._check_state(state, len(vc), int(n_iters), representation)
         if len(vc) and vc.max() > WG_VIEWS:
             return self._fit_grouped(params0, class_ids, vc, P, tgt, mask, dict(
                 n_iters=n_iters, representation=representation, prior=prior, want_points=want_points,
-                want_loss=want_loss, want_traj=want_traj))
+                want_loss=want_loss, want_traj=want_traj), state=st, t0=t0, want_state=want_state)
+        if resumable:
+            return self._fit_once(params0, class_ids, view_counts, P, tgt, mask, n_iters, representation, prior,
+                                  want_points, want_loss, want_traj, state=st, t0=t0, want_state=want_state)
         return self._fit_once(params0, class_ids, view_counts, P, tgt, mask, n_iters, representation, prior,
                               want_points, want_loss, want_traj)
 
-    def _fit_grouped(self, params0, class_ids, vc, P, tgt, mask, kw):
+    def _check_state(self, state, n, n_iters, representation):
+        """-> (device tensor [n, 32], host int32 array of the steps taken): the refusals that need the state's own words"""
+        if representation not in REPRESENTATIONS or REPRESENTATIONS[representation] > 2:
+            raise ValueError(f"a fit of representation {representation!r} cannot be resumed (super_quadric, cube and quadric can)")
+        st = state if torch.is_tensor(state) else torch.as_tensor(np.ascontiguousarray(state, np.float32))
+        if st.dim() != 2 or tuple(st.shape) != (n, STATE_FLOATS):
+            raise ValueError(f"state must be [{n}, {STATE_FLOATS}] (one row per object), got {tuple(st.shape)}")
+        st = st.to(device=self.device, dtype=torch.float32).contiguous()
+        tail = st[:, 30:32].cpu().numpy()
+        rep = REPRESENTATIONS[representation]
+        bad = np.flatnonzero(tail[:, 1] != rep)
+        if len(bad):
+            names = {v: k for k, v in REPRESENTATIONS.items()}
+            was = names.get(int(tail[bad[0], 1]), repr(float(tail[bad[0], 1])))
+            raise ValueError(f"state row {int(bad[0])} belongs to a fit of representation {was!r}, this call fits {representation!r}")
+        t0 = tail[:, 0].astype(np.int32)
+        if n and ((tail[:, 0] != t0) | (t0 < 0)).any():
+            raise ValueError("state word 30 (steps taken) is not a non-negative integer")
+        if n and int(t0.max()) + n_iters > self.max_iters:
+            i = int(t0.argmax())
+            raise _lib.OdamError(f"resumed fit: object {i} has taken {int(t0[i])} steps, {n_iters} more make {int(t0[i]) + n_iters} > "
+                                 f"max_iters {self.max_iters} of this SqFitter (code 3)")
+        return st, t0
+
+    def _fit_grouped(self, params0, class_ids, vc, P, tgt, mask, kw, state=None, t0=None, want_state=False):
         if vc.max() > MAX_VIEWS:
             raise _lib.OdamError(f"views per object must be in 1..{MAX_VIEWS}, got {vc.min()}..{vc.max()}")
         as_t = lambda x: x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
@@ -137,8 +197,12 @@ class SqFitter:
         outs = {}
         for g in groups:
             rows = np.concatenate([np.arange(offs[i], offs[i + 1]) for i in g])
+            more = {}
+            if state is not None or want_state:      # the state travels like every other per-object tensor: gathered here, scattered below
+                more = dict(state=None if state is None else state[torch.as_tensor(g, device=state.device)],
+                            t0=None if t0 is None else t0[g], want_state=want_state)
             o = self._fit_once(params0[g], [class_ids[i] for i in g], vc[g], P[rows], tgt[rows], mask[rows],
-                               kw["n_iters"], kw["representation"], kw["prior"], kw["want_points"], kw["want_loss"], kw["want_traj"])
+                               kw["n_iters"], kw["representation"], kw["prior"], kw["want_points"], kw["want_loss"], kw["want_traj"], **more)
             for key, val in o.items():
                 if val is None:
                     outs[key] = None
@@ -149,19 +213,23 @@ class SqFitter:
         return outs
 
     def _fit_once(self, params0, class_ids, view_counts, P, tgt, mask, n_iters=200, representation="super_quadric",
-                  prior=True, want_points=True, want_loss=False, want_traj=False):
+                  prior=True, want_points=True, want_loss=False, want_traj=False, state=None, t0=None, want_state=False):
         dev = self.device
         n = len(view_counts)
+        resumable = state is not None or want_state
         as_dev = lambda x, dt: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(
             device=dev, dtype=dt).contiguous()
         vc = np.asarray(view_counts, np.int64)
         if n == 0:
-            return {"params": torch.zeros(0, 9, device=dev), "points": torch.zeros(0, N_POINTS, 3, device=dev)}
+            out = {"params": torch.zeros(0, 9, device=dev), "points": torch.zeros(0, N_POINTS, 3, device=dev)}
+            if want_state:
+                out["state"] = torch.zeros(0, STATE_FLOATS, device=dev)
+            return out
         if vc.min() < 1 or vc.max() > MAX_VIEWS:
             raise _lib.OdamError(f"views per object must be in 1..{MAX_VIEWS}, got {vc.min()}..{vc.max()}")
         offs = np.zeros(n + 1, np.int32)
         offs[1:] = np.cumsum(vc)
-        d_p0 = as_dev(params0, torch.float32).reshape(n, 9)
+        d_p0 = as_dev(params0, torch.float32).reshape(n, 9) if (state is None or params0 is not None) else None
         cls = np.asarray(class_ids, np.int32).copy()
         if prior:
             if cls.min() < 0 or cls.max() > 7:
@@ -178,21 +246,41 @@ class SqFitter:
         out_pts = torch.empty(n, N_POINTS, 3, device=dev, dtype=torch.float32) if want_points else None
         loss = torch.empty(n, n_iters, device=dev, dtype=torch.float32) if want_loss else None
         traj = torch.empty(n, n_iters, 9, device=dev, dtype=torch.float32) if want_traj else None
+        st_out = torch.empty(n, STATE_FLOATS, device=dev, dtype=torch.float32) if want_state else None
+        h_t0 = None if state is None else np.ascontiguousarray(t0, np.int32)
         with torch.cuda.device(dev), self._lock:
             cur = torch.cuda.current_stream(dev)
             stream = cur.cuda_stream
             if self._last is not None and self._last[0] != stream:
                 cur.wait_event(self._last[1])     # the handle's previous launch ran on another stream: order behind it
-            _lib.check(_lib.lib().odam_sq_fit_batch(
-                self._h, ctypes.c_int(n), _lib.ptr(d_p0), _lib.ptr(d_cls), _lib.ptr(d_off), _lib.ptr(d_P),
-                _lib.ptr(d_t), _lib.ptr(d_m), _lib.ptr(self._prior_dev()), ctypes.c_int(int(n_iters)),
-                ctypes.c_int(REPRESENTATIONS[representation]), ctypes.c_int(int(vc.max())),
-                _lib.ptr(out_p), _lib.ptr(out_pts), _lib.ptr(loss), _lib.ptr(traj),
-                ctypes.c_void_p(stream)), "odam_sq_fit_batch")
+            if resumable:
+                _lib.check(_fit_resume_entry()(
+                    self._h, int(n), _lib.ptr(d_p0), _lib.ptr(d_cls), _lib.ptr(d_off), _lib.ptr(d_P),
+                    _lib.ptr(d_t), _lib.ptr(d_m), _lib.ptr(self._prior_dev()), int(n_iters),
+                    REPRESENTATIONS[representation], int(vc.max()),
+                    _lib.ptr(out_p), _lib.ptr(out_pts), _lib.ptr(loss), _lib.ptr(traj),
+                    _lib.ptr(state), None if h_t0 is None else h_t0.ctypes.data_as(ctypes.c_void_p), _lib.ptr(st_out),
+                    ctypes.c_void_p(stream)), "odam_sq_fit_resume")
+            else:
+                _lib.check(_lib.lib().odam_sq_fit_batch(
+                    self._h, ctypes.c_int(n), _lib.ptr(d_p0), _lib.ptr(d_cls), _lib.ptr(d_off), _lib.ptr(d_P),
+                    _lib.ptr(d_t), _lib.ptr(d_m), _lib.ptr(self._prior_dev()), ctypes.c_int(int(n_iters)),
+                    ctypes.c_int(REPRESENTATIONS[representation]), ctypes.c_int(int(vc.max())),
+                    _lib.ptr(out_p), _lib.ptr(out_pts), _lib.ptr(loss), _lib.ptr(traj),
+                    ctypes.c_void_p(stream)), "odam_sq_fit_batch")
             ev = torch.cuda.Event()
             ev.record(cur)
             self._last = (stream, ev)
-        return {"params": out_p, "points": out_pts, "loss": loss, "traj": traj}
+        out = {"params": out_p, "points": out_pts, "loss": loss, "traj": traj}
+        if want_state:
+            out["state"] = st_out
+        return out
+
+    def last_launch(self):
+        """shape of the newest fit launch (odam_sq_last_launch): grid, threads per workgroup, workgroups per object, longest-first flag"""
+        s4 = (ctypes.c_int * 4)()
+        _lib.check(_lib.lib().odam_sq_last_launch(self._h, s4), "odam_sq_last_launch")
+        return {"grid": s4[0], "threads": s4[1], "split": s4[2], "ordered": bool(s4[3])}
 
     def fit_dual(self, init5, half_dims, view_counts, P, tgt, mask, n_iters=500, want_loss=False, want_traj=False,
                  check=True):
