@@ -5,7 +5,8 @@
 // GNN layers between tracks and detections (4 heads of 64), final projection, score matrix / 16, 100 Sinkhorn
 // iterations in log space.  The reference runs ~300 tiny PyTorch kernels per frame for this; here every Conv1d(k=1)
 // is a conv_gemm launch (fp32 MFMA), attention is the fused kernel with head dimension 64, and the whole Sinkhorn
-// loop is ONE single-workgroup kernel.  The Hungarian step stays on the host (scipy, as the reference).
+// loop is ONE single-workgroup kernel (assoc_sinkhorn.hip).  Beside this file: the track-window store that builds the network's
+// track input (assoc_trackwin.hip) and the Hungarian / attach step behind it (assoc_match.hip).
 //
 // Layout: token-major rows.  A token set lives in a [N, 512] buffer "cat": columns 0..255 hold x, columns
 // 256..511 receive the attention message, so cat([x, message]) (associator.py:97) needs no copy.
@@ -19,12 +20,13 @@
 #include <vector>
 
 #include "../../include/odam_assoc.h"
+#include "assoc_internal.h"
 #include "conv_gemm.h"
 #include "detr_kernels.h"
-#include "sk_wave.h"
 #include "odam_config.h"
 #include "odam_err.h"
 
+using namespace odam_assoc_internal;      // launch_sinkhorn, PG_GROUPS, PG_BAR_WORDS
 using odam_cg::ConvGemmArgs;
 
 namespace {
@@ -80,73 +82,6 @@ __global__ __launch_bounds__(256) void time_mean_kernel(const float* __restrict_
     out[(size_t)s * 512 + c] = acc / (float)L;
 }
 
-// log_optimal_transport + log_sinkhorn_iterations (associator.py:283-312), one 1024-thread workgroup:
-//   couplings Z[(m+1) x (n+1)] = [[scores, alpha], [alpha, alpha]] in LDS; u, v in LDS;
-//   iters x { u = log_mu - logsumexp_j(Z + v);  v = log_nu - logsumexp_i(Z + u) };  out = Z + u + v - norm
-// A row (or column) is reduced by a group of 8 lanes (xor butterflies inside the group), 128 groups at a time.
-constexpr int SK_NT = 1024, SK_G = 8;
-
-__device__ __forceinline__ float group_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 1)); v = fmaxf(v, __shfl_xor(v, 2)); v = fmaxf(v, __shfl_xor(v, 4));
-    return v;
-}
-__device__ __forceinline__ float group_sum(float v) {
-    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
-    return v;
-}
-
-__global__ __launch_bounds__(SK_NT) void sinkhorn_kernel(const float* __restrict__ scores, int lds, int m, int n,
-                                                         float alpha, int iters, float* __restrict__ out,
-                                                         const int* __restrict__ n_dev, const unsigned* __restrict__ err, unsigned* lost_count) {
-    extern __shared__ float sm[];
-    if (n_dev) n = *n_dev;      // replayed from a captured graph: the number of detections of THIS frame lives in memory
-    const int M1 = m + 1, N1 = n + 1;
-    float* Z = sm;                 // [M1][N1]
-    float* u = Z + M1 * N1;        // [M1]
-    float* v = u + M1;             // [N1]
-    const int tid = threadIdx.x;
-    for (int i = tid; i < M1 * N1; i += SK_NT) {
-        const int r = i / N1, c = i - r * N1;
-        Z[i] = (r < m && c < n) ? scores[(size_t)r * lds + c] : alpha;
-    }
-    for (int i = tid; i < M1; i += SK_NT) u[i] = 0.0f;
-    for (int i = tid; i < N1; i += SK_NT) v[i] = 0.0f;
-    const float norm = -logf((float)m + (float)n);
-    const float log_mu_last = logf((float)n) + norm, log_nu_last = logf((float)m) + norm;
-    __syncthreads();
-    const int grp = tid / SK_G, gl = tid % SK_G;
-    constexpr int NG = SK_NT / SK_G;
-    for (int it = 0; it < iters; ++it) {
-        for (int r0 = 0; r0 < M1; r0 += NG) {            // u: one group per row
-            const int r = r0 + grp;
-            float mx = -INFINITY;
-            if (r < M1) for (int c = gl; c < N1; c += SK_G) mx = fmaxf(mx, Z[r * N1 + c] + v[c]);
-            mx = group_max(mx);
-            float sum = 0.0f;
-            if (r < M1) for (int c = gl; c < N1; c += SK_G) sum += expf(Z[r * N1 + c] + v[c] - mx);
-            sum = group_sum(sum);
-            if (r < M1 && gl == 0) u[r] = ((r < m) ? norm : log_mu_last) - (logf(sum) + mx);
-        }
-        __syncthreads();
-        for (int c0 = 0; c0 < N1; c0 += NG) {            // v: one group per column
-            const int c = c0 + grp;
-            float mx = -INFINITY;
-            if (c < N1) for (int r = gl; r < M1; r += SK_G) mx = fmaxf(mx, Z[r * N1 + c] + u[r]);
-            mx = group_max(mx);
-            float sum = 0.0f;
-            if (c < N1) for (int r = gl; r < M1; r += SK_G) sum += expf(Z[r * N1 + c] + u[r] - mx);
-            sum = group_sum(sum);
-            if (c < N1 && gl == 0) v[c] = ((c < n) ? norm : log_nu_last) - (logf(sum) + mx);
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < M1 * N1; i += SK_NT) {
-        const int r = i / N1, c = i - r * N1;
-        out[i] = (err && *err) ? NAN : Z[i] + u[r] + v[c] - norm;     // the matching kernel's launch was lost (grid_barrier): fail loudly downstream
-    }
-    if (tid == 0 && err && *err && lost_count) __hip_atomic_fetch_add(lost_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // ---- the matching GNN + final projection as ONE persistent launch ----------------------------------------
 // At 40 tracks the GNN is 8 layers x 6 launches on <= 70 rows: every launch is a dispatch and a memory round trip long
 // (~10 us) however little it computes.  This kernel keeps PG_WG workgroups resident (one per CU) and walks the same stages
@@ -162,9 +97,7 @@ __global__ __launch_bounds__(SK_NT) void sinkhorn_kernel(const float* __restrict
 // write back and invalidate the whole L2 40 times per launch, weights included.  The weights are read-only: plain loads.
 // Barrier: two levels -- 8 group counters (workgroup id % 8; 32 arrivals each on its own line), the last arrival of a group
 // bumps the global generation every workgroup polls; the spin is bounded so a lost workgroup cannot hang the device.
-constexpr int PG_WG = 256, PG_NT = 256, PG_NW = PG_NT / 64, PG_MAXL = 16, PG_GROUPS = 8;
-constexpr int PG_BAR_WORDS = 32 * (2 + 2 * PG_GROUPS);     // generation + flag line, 8 group counters, 8 per-XCD counters (each on its own 128-byte line),
-                                                           // one line of 8 placement words (gnn_rowpart_kernel: XCC id + 1 of each group)
+constexpr int PG_WG = 256, PG_NT = 256, PG_NW = PG_NT / 64, PG_MAXL = 16;      // PG_GROUPS, PG_BAR_WORDS (the barrier words): assoc_internal.h
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct GnnLayerW { const float *qkv_w, *qkv_b, *mg_w, *mg_b, *m0_w, *m0_b, *m2_w, *m2_b; int cross; };
@@ -179,7 +112,6 @@ struct GnnArgs {
     unsigned long long timeout_ticks; // bound of one barrier wait in 100 MHz ticks (0: give up at the first barrier -- tests)
     unsigned long long* stamps;       // diagnostics (odam_assoc_stage_stamps): 100 MHz timer of workgroup 0 after every stage, or null
     int fake_misplaced;               // tests (odam_assoc_debug_misplace): gnn_rowpart_kernel's placement check behaves as if a group straddled XCDs
-    int merged;                       // odam_config assoc.merge: m0_w / m0_b hold [W0x | W0m Wm] / b0 + W0m bm, the attention writes into X[:, 256:], no merge stage
 };
 
 constexpr int SC1 = 16;      // cache-policy bit of the buffer intrinsics on gfx94x / gfx950
@@ -227,22 +159,28 @@ __device__ __forceinline__ bool grid_barrier(unsigned* bar, unsigned& target, un
     return *lost == 0;
 }
 
-// Y[M, N] = act((X[M, K] W[N, K]^T) * scale + b (+ res)); one 16x16 output block per workgroup, wave w takes k in
-// [w K / 4, (w + 1) K / 4).  v_mfma_f32_16x16x4_f32: lane l carries A[row l % 16][k l / 16] and B[col l % 16][k l / 16]; a
-// lane's 16-byte load holds the k slots of four consecutive instructions (A and B permute k the same way).
-// X, res and Y are exchanged between workgroups (sc1); W is read-only (plain, cached).
+// The stages of a GNN layer, ONE set for both persistent kernels: a stage works on the rows [r0, r0 + nR) and deals its items to the
+// caller's workers (first item, stride).  gnn_persistent_kernel passes all rows and all 256 workgroups, gnn_rowpart_kernel the rows of
+// its XCD and that XCD's 32 workgroups; an output element is computed by the same instructions either way: the kernels agree bit for bit.
+// FAR: the output is read by workgroups behind ANOTHER L2 before the next device-wide barrier, so it is stored sc1 (written through to
+// the coherence point); otherwise the readers share this XCD's L2, and a plain store, drained by the XCD-local barrier, is enough.
+// Rows that were exchanged are always LOADED sc1 (past the non-coherent vector L1); the weights are read-only: plain, cached.
+//
+// Y[r0 .. r0 + nR, N] = act(X W[N, K]^T + b (+ res)); one 16x16 output block per workgroup and item (wi, then every nw-th), wave w
+// takes k in [w K / 4, (w + 1) K / 4).  v_mfma_f32_16x16x4_f32: lane l carries A[row l % 16][k l / 16] and B[col l % 16][k l / 16];
+// a lane's 16-byte load holds the k slots of four consecutive instructions (A and B permute k the same way).
 // (One ascending-k chain per output on a single wave was tried as well: 386 us per launch instead of 250.)
-template <int K, bool RELU>
-__device__ void stage_gemm(const float* X, int lda, const float* W, const float* b, int M, int N, const float* res, float* Y,
-                           int ldc, float* red, int wave, int lane) {
+template <int K, bool RELU, bool FAR>
+__device__ void stage_gemm(const float* X, int lda, const float* W, const float* b, int r0, int nR, int N, const float* res,
+                           float* Y, int ldc, float* red, int wave, int lane, int wi, int nw) {
     constexpr int KW = K / PG_NW, NL = KW / 16;            // k per wave, 16-byte loads per lane and operand
-    const int RB = (M + 15) >> 4, CB = N >> 4;
+    const int RB = (nR + 15) >> 4, CB = N >> 4, rlim = r0 + nR;
     const int li = lane & 15, kq = lane >> 4;
     const __amdgpu_buffer_rsrc_t xb = coh_buf(X), yb = coh_buf(Y), rsb = coh_buf(res ? res : Y);
-    for (int item = blockIdx.x; item < RB * CB; item += PG_WG) {
+    for (int item = wi; item < RB * CB; item += nw) {
         const int rb = item / CB, cb = item - rb * CB;
-        const int r = rb * 16 + li;
-        const int xo = (r < M ? r : M - 1) * lda + wave * KW + 4 * kq;
+        const int r = r0 + rb * 16 + li;
+        const int xo = (r < rlim ? r : rlim - 1) * lda + wave * KW + 4 * kq;
         const float* wp = W + (size_t)(cb * 16 + li) * K + wave * KW + 4 * kq;
         float4 a[NL], w[NL];
 #pragma unroll
@@ -269,12 +207,13 @@ __device__ void stage_gemm(const float* X, int lda, const float* W, const float*
             const float bias = b ? b[col] : 0.0f;
 #pragma unroll
             for (int i = 0; i < 4; i++) {      // accumulator register i of lane l: row 4 (l / 16) + i, column l % 16
-                const int row = rb * 16 + 4 * kq + i;
-                if (row < M) {
+                const int row = r0 + rb * 16 + 4 * kq + i;
+                if (row < rlim) {
                     float v = tot[i] + bias;
                     if (res) v += coh_ld(rsb, row * ldc + col);
                     if (RELU) v = fmaxf(v, 0.0f);
-                    coh_st(yb, row * ldc + col, v);
+                    if (FAR) coh_st(yb, row * ldc + col, v);
+                    else Y[(size_t)row * ldc + col] = v;
                 }
             }
         }
@@ -293,15 +232,15 @@ __device__ __forceinline__ float wave_sum64(float v) {
     return v;
 }
 
-// softmax(Q K^T / 8) V per (query row, head), head dimension 64 (associator.py:75-82); one wavefront per item:
-// lane j scores key j, lane d accumulates output channel d, 64 source rows at a time (online softmax across chunks);
-// the key rows and the value columns of a chunk are all in flight together.  sc: this wave's LDS strip [64].
-template <int ldatt>
-__device__ void stage_attn(const float* kv, int T, int cross, float* att, float* sc, int wave_g, int lane) {
-    const int MX = T + ND;
-    const __amdgpu_buffer_rsrc_t kb = coh_buf(kv), ab = coh_buf(att);
-    for (int item = wave_g; item < MX * 4; item += PG_WG * PG_NW) {
-        const int q = item >> 2, hd = item & 3;
+// softmax(Q K^T / 8) V per (query row, head) for the queries [r0, r0 + nR), head dimension 64 (associator.py:75-82); one wavefront
+// per item (wave_x, then every n_waves-th): lane j scores key j, lane d accumulates output channel d, 64 source rows at a time (online
+// softmax across chunks); the key rows and the value columns of a chunk are all in flight together.  Keys and values of every row
+// come from kv (sc1 loads).  sc: this wave's LDS strip [64].
+template <int ldatt, bool FAR>
+__device__ void stage_attn(const float* kv, int T, int cross, float* att, float* sc, int r0, int nR, int wave_x, int n_waves, int lane) {
+    const __amdgpu_buffer_rsrc_t kb = coh_buf(kv);
+    for (int item = wave_x; item < nR * 4; item += n_waves) {
+        const int q = r0 + (item >> 2), hd = item & 3;
         const bool is_track = q < T;
         const bool src_tracks = is_track != (cross != 0);
         const int src0 = src_tracks ? 0 : T, nsrc = src_tracks ? T : ND;
@@ -338,17 +277,21 @@ __device__ void stage_attn(const float* kv, int T, int cross, float* att, float*
             for (int jj = 0; jj < 64; jj++) o += (jj < nj ? sc[jj] : 0.0f) * vv[jj];
             __builtin_amdgcn_wave_barrier();
         }
-        coh_st(ab, q * ldatt + hd * 64 + lane, o / run_sum);
+        if (FAR) coh_st(coh_buf(att), q * ldatt + hd * 64 + lane, o / run_sum);
+        else att[(size_t)q * ldatt + hd * 64 + lane] = o / run_sum;
     }
 }
 
-template <bool MERGED>      // odam_config assoc.merge (two instantiations: one kernel holding both forms went from 245 to 248 + 32 registers and 256 B of scratch)
+// MERGED = odam_config assoc.merge: m0_w / m0_b hold [W0x | W0m Wm] / b0 + W0m bm, the attention writes into X[:, 256:], no merge stage
+// (two instantiations: one kernel holding both forms went from 245 to 248 + 32 registers and 256 B of scratch)
+template <bool MERGED>
 __global__ __launch_bounds__(PG_NT) void gnn_persistent_kernel(GnnArgs a) {
     __shared__ float red[(PG_NW - 1) * 64 * 4];
     __shared__ float scs[PG_NW * 64];
     __shared__ int lost;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_g = wave * PG_WG + blockIdx.x;          // consecutive attention items go to different workgroups
+    const int wi = blockIdx.x, nw = PG_WG;                 // every stage: all rows, dealt to all workgroups, stored FAR
+    const int wave_g = wave * PG_WG + blockIdx.x, n_waves = PG_WG * PG_NW;      // consecutive attention items go to different workgroups
     unsigned target = 0;
     const int T = a.T, MX = T + ND;
     int n_stamp = 0;
@@ -358,24 +301,23 @@ __global__ __launch_bounds__(PG_NT) void gnn_persistent_kernel(GnnArgs a) {
     float* sc = scs + wave * 64;
     for (int l = 0; l < a.n_layers; l++) {
         const GnnLayerW& P = a.L[l];
-        stage_gemm<D, false>(a.X, 512, P.qkv_w, P.qkv_b, MX, 3 * D, nullptr, a.kv, 3 * D, red, wave, lane);
+        stage_gemm<D, false, true>(a.X, 512, P.qkv_w, P.qkv_b, 0, MX, 3 * D, nullptr, a.kv, 3 * D, red, wave, lane, wi, nw);
         PG_BARRIER();
         if constexpr (MERGED) {      // the attention's rows ARE the second half of the MLP's input (merge folded into m0_w)
-            stage_attn<512>(a.kv, T, P.cross, a.X + D, sc, wave_g, lane);
+            stage_attn<512, true>(a.kv, T, P.cross, a.X + D, sc, 0, MX, wave_g, n_waves, lane);
             PG_BARRIER();
         } else {
-            stage_attn<256>(a.kv, T, P.cross, a.att, sc, wave_g, lane);
+            stage_attn<256, true>(a.kv, T, P.cross, a.att, sc, 0, MX, wave_g, n_waves, lane);
             PG_BARRIER();
-            stage_gemm<D, false>(a.att, D, P.mg_w, P.mg_b, MX, D, nullptr, a.X + D, 512, red, wave, lane);
+            stage_gemm<D, false, true>(a.att, D, P.mg_w, P.mg_b, 0, MX, D, nullptr, a.X + D, 512, red, wave, lane, wi, nw);
             PG_BARRIER();
         }
-        stage_gemm<2 * D, true>(a.X, 512, P.m0_w, P.m0_b, MX, 2 * D, nullptr, a.h, 2 * D, red, wave, lane);
+        stage_gemm<2 * D, true, true>(a.X, 512, P.m0_w, P.m0_b, 0, MX, 2 * D, nullptr, a.h, 2 * D, red, wave, lane, wi, nw);
         PG_BARRIER();
-        stage_gemm<2 * D, false>(a.h, 2 * D, P.m2_w, P.m2_b, MX, D, a.X, a.X, 512, red, wave, lane);
+        stage_gemm<2 * D, false, true>(a.h, 2 * D, P.m2_w, P.m2_b, 0, MX, D, a.X, a.X, 512, red, wave, lane, wi, nw);
         PG_BARRIER();
     }
-#undef PG_BARRIER
-    stage_gemm<D, false>(a.X, 512, a.fin_w, a.fin_b, MX, D, nullptr, a.mT, D, red, wave, lane);
+    stage_gemm<D, false, true>(a.X, 512, a.fin_w, a.fin_b, 0, MX, D, nullptr, a.mT, D, red, wave, lane, wi, nw);
     stamp();
 }
 
@@ -386,8 +328,8 @@ __global__ __launch_bounds__(PG_NT) void gnn_persistent_kernel(GnnArgs a) {
 // in that L2 -- costs 1.1 us where the device-wide form costs 4.9 (tests/native/xcd_barrier_probe.hip).  So XCD x owns rows
 // [x R, (x + 1) R), R = ceil(rows / 8): its workgroups project q | k | v of those rows (stored sc1: the one thing that crosses XCDs),
 // all 256 workgroups meet ONCE, then attention, merge and the two MLP layers of those rows run behind XCD-local barriers.  Every
-// output element is computed exactly as in gnn_persistent_kernel (same 16x16 blocks, same K split over the four waves): the two
-// kernels agree bit for bit.  k | v alternate between two buffers by layer: a fast XCD may project layer l + 1 while a slow one still
+// output element is computed by the stage functions gnn_persistent_kernel calls (same 16x16 blocks, same K split over the four
+// waves): the two kernels agree bit for bit.  k | v alternate between two buffers by layer: a fast XCD may project layer l + 1 while a slow one still
 // reads layer l's keys (the device barrier of layer l + 1 is what frees buffer l & 1 again).
 __device__ __forceinline__ bool xcd_barrier(unsigned* bar, unsigned* cnt, unsigned& target, unsigned long long timeout_ticks, int* lost) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's stores have reached the L2 the readers will hit
@@ -413,106 +355,6 @@ __device__ __forceinline__ bool xcd_barrier(unsigned* bar, unsigned* cnt, unsign
     return *lost == 0;
 }
 
-// stage_gemm over rows [r0, r0 + nR) only, blocks dealt over the nw workgroups of this XCD (wi = 0 .. nw - 1); FAR: the output is read
-// by other XCDs (sc1 store), otherwise a plain store that the XCD-local barrier drains
-template <int K, bool RELU, bool FAR>
-__device__ void stage_gemm_rows(const float* X, int lda, const float* W, const float* b, int r0, int nR, int N, const float* res,
-                                float* Y, int ldc, float* red, int wave, int lane, int wi, int nw) {
-    constexpr int KW = K / PG_NW, NL = KW / 16;
-    const int RB = (nR + 15) >> 4, CB = N >> 4, rlim = r0 + nR;
-    const int li = lane & 15, kq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t xb = coh_buf(X), yb = coh_buf(Y), rsb = coh_buf(res ? res : Y);
-    for (int item = wi; item < RB * CB; item += nw) {
-        const int rb = item / CB, cb = item - rb * CB;
-        const int r = r0 + rb * 16 + li;
-        const int xo = (r < rlim ? r : rlim - 1) * lda + wave * KW + 4 * kq;
-        const float* wp = W + (size_t)(cb * 16 + li) * K + wave * KW + 4 * kq;
-        float4 a[NL], w[NL];
-#pragma unroll
-        for (int t = 0; t < NL; t++) {
-            a[t] = coh_ld4(xb, xo + 16 * t);
-            w[t] = *reinterpret_cast<const float4*>(wp + 16 * t);
-        }
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < NL; t++) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].x, w[t].x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].y, w[t].y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].z, w[t].z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].w, w[t].w, acc1, 0, 0, 0);
-        }
-        const f32x4 part = acc0 + acc1;
-        if (wave) *reinterpret_cast<f32x4*>(red + ((wave - 1) * 64 + lane) * 4) = part;
-        __syncthreads();
-        if (wave == 0) {
-            f32x4 tot = part;
-#pragma unroll
-            for (int w2 = 0; w2 < PG_NW - 1; w2++) tot += *reinterpret_cast<const f32x4*>(red + (w2 * 64 + lane) * 4);
-            const int col = cb * 16 + li;
-            const float bias = b ? b[col] : 0.0f;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int row = r0 + rb * 16 + 4 * kq + i;
-                if (row < rlim) {
-                    float v = tot[i] + bias;
-                    if (res) v += coh_ld(rsb, row * ldc + col);
-                    if (RELU) v = fmaxf(v, 0.0f);
-                    if (FAR) coh_st(yb, row * ldc + col, v);
-                    else Y[(size_t)row * ldc + col] = v;
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// stage_attn for the queries [r0, r0 + nR) (items dealt over the n_waves wavefronts of this XCD); keys and values of every row come
-// from kv (sc1 loads), the output stays in this XCD (plain store)
-template <int ldatt>
-__device__ void stage_attn_rows(const float* kv, int T, int cross, float* att, float* sc, int r0, int nR, int wave_x, int n_waves, int lane) {
-    const __amdgpu_buffer_rsrc_t kb = coh_buf(kv);
-    for (int item = wave_x; item < nR * 4; item += n_waves) {
-        const int q = r0 + (item >> 2), hd = item & 3;
-        const bool is_track = q < T;
-        const bool src_tracks = is_track != (cross != 0);
-        const int src0 = src_tracks ? 0 : T, nsrc = src_tracks ? T : ND;
-        const int qo = q * 768 + hd * 64;
-        float4 qq[16];
-#pragma unroll
-        for (int d = 0; d < 16; d++) qq[d] = coh_ld4(kb, qo + 4 * d);
-        float run_max = -INFINITY, run_sum = 0.0f, o = 0.0f;
-        for (int j0 = 0; j0 < nsrc; j0 += 64) {
-            const int j = j0 + lane, nj = nsrc - j0 < 64 ? nsrc - j0 : 64;
-            const int ko = (src0 + (j < nsrc ? j : nsrc - 1)) * 768 + 256 + hd * 64;
-            const int vo = (src0 + j0) * 768 + 512 + hd * 64 + lane;
-            float4 kk[16];
-            float vv[64];
-#pragma unroll
-            for (int d = 0; d < 16; d++) kk[d] = coh_ld4(kb, ko + 4 * d);
-#pragma unroll
-            for (int jj = 0; jj < 64; jj++) vv[jj] = coh_ld(kb, vo + (jj < nj ? jj : nj - 1) * 768);
-            float acc = 0.0f;
-#pragma unroll
-            for (int d = 0; d < 16; d++) {
-                acc += qq[d].x * kk[d].x; acc += qq[d].y * kk[d].y; acc += qq[d].z * kk[d].z; acc += qq[d].w * kk[d].w;
-            }
-            const float sdot = j < nsrc ? acc * 0.125f : -INFINITY;
-            const float mx = fmaxf(run_max, wave_max64(sdot));
-            const float p = j < nsrc ? expf(sdot - mx) : 0.0f;
-            const float corr = expf(run_max - mx);
-            run_sum = run_sum * corr + wave_sum64(p);
-            run_max = mx;
-            sc[lane] = p;
-            __builtin_amdgcn_wave_barrier();
-            o *= corr;
-#pragma unroll
-            for (int jj = 0; jj < 64; jj++) o += (jj < nj ? sc[jj] : 0.0f) * vv[jj];
-            __builtin_amdgcn_wave_barrier();
-        }
-        att[(size_t)q * ldatt + hd * 64 + lane] = o / run_sum;
-    }
-}
-
 template <bool MERGED>
 __global__ __launch_bounds__(PG_NT) void gnn_rowpart_kernel(GnnArgs a) {
     __shared__ float red[(PG_NW - 1) * 64 * 4];
@@ -528,7 +370,6 @@ __global__ __launch_bounds__(PG_NT) void gnn_rowpart_kernel(GnnArgs a) {
     unsigned* cnt_x = a.bar + 32 * (1 + PG_GROUPS + xcd);
     int n_stamp = 0;
     auto stamp = [&] { if (a.stamps && blockIdx.x == 0 && tid == 0) a.stamps[n_stamp++] = wall_clock64(); };
-#define PG_BARRIER() do { if (!grid_barrier(a.bar, target, a.timeout_ticks, &lost)) return; stamp(); } while (0)
 #define PX_BARRIER() do { if (!xcd_barrier(a.bar, cnt_x, target_x, a.timeout_ticks, &lost)) return; stamp(); } while (0)
     // Placement check.  The XCD-local stages below are exchanged with plain stores and a workgroup-scope counter, which is right only
     // if the 32 workgroups of a group (equal blockIdx mod 8) run behind ONE L2.  That is how the dispatcher has always placed a plain
@@ -548,316 +389,26 @@ __global__ __launch_bounds__(PG_NT) void gnn_rowpart_kernel(GnnArgs a) {
     for (int l = 0; l < a.n_layers; l++) {
         const GnnLayerW& P = a.L[l];
         float* kv = (l & 1) ? a.kv2 : a.kv;
-        stage_gemm_rows<D, false, true>(a.X, 512, P.qkv_w, P.qkv_b, r0, nR, 3 * D, nullptr, kv, 3 * D, red, wave, lane, wi, nw);
+        stage_gemm<D, false, true>(a.X, 512, P.qkv_w, P.qkv_b, r0, nR, 3 * D, nullptr, kv, 3 * D, red, wave, lane, wi, nw);
         PG_BARRIER();
         if constexpr (MERGED) {
-            stage_attn_rows<512>(kv, T, P.cross, a.X + D, sc, r0, nR, wave_x, n_waves, lane);
+            stage_attn<512, false>(kv, T, P.cross, a.X + D, sc, r0, nR, wave_x, n_waves, lane);
             PX_BARRIER();
         } else {
-            stage_attn_rows<256>(kv, T, P.cross, a.att, sc, r0, nR, wave_x, n_waves, lane);
+            stage_attn<256, false>(kv, T, P.cross, a.att, sc, r0, nR, wave_x, n_waves, lane);
             PX_BARRIER();
-            stage_gemm_rows<D, false, false>(a.att, D, P.mg_w, P.mg_b, r0, nR, D, nullptr, a.X + D, 512, red, wave, lane, wi, nw);
+            stage_gemm<D, false, false>(a.att, D, P.mg_w, P.mg_b, r0, nR, D, nullptr, a.X + D, 512, red, wave, lane, wi, nw);
             PX_BARRIER();
         }
-        stage_gemm_rows<2 * D, true, false>(a.X, 512, P.m0_w, P.m0_b, r0, nR, 2 * D, nullptr, a.h, 2 * D, red, wave, lane, wi, nw);
+        stage_gemm<2 * D, true, false>(a.X, 512, P.m0_w, P.m0_b, r0, nR, 2 * D, nullptr, a.h, 2 * D, red, wave, lane, wi, nw);
         PX_BARRIER();
-        stage_gemm_rows<2 * D, false, false>(a.h, 2 * D, P.m2_w, P.m2_b, r0, nR, D, a.X, a.X, 512, red, wave, lane, wi, nw);
+        stage_gemm<2 * D, false, false>(a.h, 2 * D, P.m2_w, P.m2_b, r0, nR, D, a.X, a.X, 512, red, wave, lane, wi, nw);
         PX_BARRIER();
     }
 #undef PG_BARRIER
 #undef PX_BARRIER
-    stage_gemm_rows<D, false, false>(a.X, 512, a.fin_w, a.fin_b, r0, nR, D, nullptr, a.mT, D, red, wave, lane, wi, nw);
+    stage_gemm<D, false, false>(a.X, 512, a.fin_w, a.fin_b, r0, nR, D, nullptr, a.mT, D, red, wave, lane, wi, nw);
     stamp();
-}
-
-// ---- Sinkhorn for at most 31 columns (the associator's case: <= 30 detections + dustbin) ----------------------------------
-// Same iteration as sinkhorn_kernel; what differs is who reduces what.  A row (<= 32 entries) is one 16-lane DPP row of a
-// wavefront, two columns per lane: four rows per wavefront, 64 rows per sweep of the 16 waves, reduced by quad permutes and
-// half-row / row mirrors alone (register-file speed).  A wavefront takes two columns at once, lane = row; its 64-lane
-// reductions finish through v_readlane.  No ds_bpermute is left on the dependent path of an iteration, and Z is stored with
-// an odd row stride so that a column walks all LDS banks.  Measured per 100 iterations: DESIGN.md section 4.
-__device__ __forceinline__ float dpp_f(float v, int ctrl_sel) {
-    const int x = __builtin_bit_cast(int, v);
-    int r;
-    switch (ctrl_sel) {
-        case 0: r = __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xf, 0xf, false); break;     // quad_perm [1,0,3,2]
-        case 1: r = __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xf, 0xf, false); break;     // quad_perm [2,3,0,1]
-        case 2: r = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xf, 0xf, false); break;    // row_half_mirror
-        default: r = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xf, 0xf, false); break;   // row_mirror
-    }
-    return __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float max16(float v) {
-    v = fmaxf(v, dpp_f(v, 0)); v = fmaxf(v, dpp_f(v, 1)); v = fmaxf(v, dpp_f(v, 2)); v = fmaxf(v, dpp_f(v, 3));
-    return v;
-}
-__device__ __forceinline__ float sum16(float v) {
-    v += dpp_f(v, 0); v += dpp_f(v, 1); v += dpp_f(v, 2); v += dpp_f(v, 3);
-    return v;
-}
-
-// exp / log of the iteration: the hardware's v_exp_f32 / v_log_f32 (through exp2 / log2).  The library functions are a
-// range reduction and a polynomial each -- four of them sit on the dependent path of every iteration and were most of its
-// 1.9 us; arguments here are (x - max) <= 0 and sums in [1, 64], where the hardware forms are good to ~1e-6 relative.
-#define SK_EXP(x) __expf(x)
-#define SK_LOG(x) __logf(x)
-__global__ __launch_bounds__(SK_NT) void sinkhorn32_kernel(const float* __restrict__ scores, int lds, int m, int n,
-                                                           float alpha, int iters, float* __restrict__ out,
-                                                           const int* __restrict__ n_dev, const unsigned* __restrict__ err, unsigned* lost_count) {
-    extern __shared__ float sm[];
-    if (n_dev) n = *n_dev;
-    const int M1 = m + 1, N1 = n + 1;       // N1 <= 32
-    constexpr int ZS = 33;
-    float* Z = sm;                          // [M1][33]
-    float* u = Z + (size_t)M1 * ZS;         // [M1]
-    float* v = u + M1;                      // [32]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int NWV = SK_NT / 64;
-    for (int i = tid; i < M1 * N1; i += SK_NT) {
-        const int r = i / N1, c = i - r * N1;
-        Z[r * ZS + c] = (r < m && c < n) ? scores[(size_t)r * lds + c] : alpha;
-    }
-    for (int i = tid; i < M1; i += SK_NT) u[i] = 0.0f;
-    if (tid < 32) v[tid] = 0.0f;
-    const float norm = -logf((float)m + (float)n);
-    const float log_mu_last = logf((float)n) + norm, log_nu_last = logf((float)m) + norm;
-    __syncthreads();
-    const int q4 = lane >> 4, l16 = lane & 15;
-    // 64-lane reductions: DPP inside the four 16-lane rows, then the four row results through SGPRs (v_readlane) --
-    // no ds_bpermute on the dependent path
-    auto max64 = [](float x) {
-        x = max16(x);
-        const float a0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 0));
-        const float a1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 16));
-        const float a2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 32));
-        const float a3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 48));
-        return fmaxf(fmaxf(a0, a1), fmaxf(a2, a3));
-    };
-    auto sum64 = [](float x) {
-        x = sum16(x);
-        const float a0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 0));
-        const float a1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 16));
-        const float a2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 32));
-        const float a3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 48));
-        return (a0 + a1) + (a2 + a3);
-    };
-    for (int it = 0; it < iters; ++it) {
-        // u: four rows per wavefront, one per 16-lane DPP row; a lane holds columns l16 and l16 + 16 of its row
-        for (int r0 = 4 * wave; r0 < M1; r0 += 4 * NWV) {
-            const int r = r0 + q4;
-            const bool ok0 = r < M1 && l16 < N1, ok1 = r < M1 && l16 + 16 < N1;
-            const float x0 = ok0 ? Z[r * ZS + l16] + v[l16] : -INFINITY;
-            const float x1 = ok1 ? Z[r * ZS + l16 + 16] + v[l16 + 16] : -INFINITY;
-            const float mx = max16(fmaxf(x0, x1));
-            const float e = sum16((ok0 ? SK_EXP(x0 - mx) : 0.0f) + (ok1 ? SK_EXP(x1 - mx) : 0.0f));
-            if (r < M1 && l16 == 0) u[r] = ((r < m) ? norm : log_mu_last) - (SK_LOG(e) + mx);
-        }
-        __syncthreads();
-        // v: columns wave and wave + 16 on this wavefront (two independent chains), lane = row
-        {
-            const int c0 = wave, c1 = wave + NWV;
-            const bool h0 = c0 < N1, h1 = c1 < N1;
-            float m0 = -INFINITY, m1 = -INFINITY;
-            for (int r = lane; r < M1; r += 64) {
-                const float ur = u[r];
-                if (h0) m0 = fmaxf(m0, Z[r * ZS + c0] + ur);
-                if (h1) m1 = fmaxf(m1, Z[r * ZS + c1] + ur);
-            }
-            m0 = max64(m0); m1 = max64(m1);
-            float e0 = 0.0f, e1 = 0.0f;
-            for (int r = lane; r < M1; r += 64) {
-                const float ur = u[r];
-                if (h0) e0 += SK_EXP(Z[r * ZS + c0] + ur - m0);
-                if (h1) e1 += SK_EXP(Z[r * ZS + c1] + ur - m1);
-            }
-            e0 = sum64(e0); e1 = sum64(e1);
-            if (lane == 0) {
-                if (h0) v[c0] = ((c0 < n) ? norm : log_nu_last) - (SK_LOG(e0) + m0);
-                if (h1) v[c1] = ((c1 < n) ? norm : log_nu_last) - (SK_LOG(e1) + m1);
-            }
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < M1 * N1; i += SK_NT) {
-        const int r = i / N1, c = i - r * N1;
-        out[i] = (err && *err) ? NAN : Z[r * ZS + c] + u[r] + v[c] - norm;
-    }
-    // ... and tell the host (pinned counter, read after the stream has been synchronised: odam_assoc_lost_launches)
-    if (tid == 0 && err && *err && lost_count) __hip_atomic_fetch_add(lost_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ---- Sinkhorn on ONE wavefront: <= 128 rows, <= 32 columns -----------------------------------------------------------------------
-// The iteration of log_sinkhorn_iterations (associator.py:283-312) on scaling factors instead of potentials.  With
-// K_rc = exp(Z_rc + u_r + v_c) (the coupling at the potentials reached so far), a_r, b_c the factors since then, an iteration is
-//     a_r = mu_r / sum_c K_rc b_c        b_c = nu_c / sum_r K_rc a_r
-// -- multiply-adds and two reciprocals; no exp / log / max, no LDS and no barrier.  Every J iterations the factors are ABSORBED:
-// u += log a, v += log b, K recomputed from Z, u, v, a = b = 1.  In exact arithmetic this is the log-space iteration; in float32
-// it stays so as long as the factors of J iterations stay far inside the float range (they are checked at every absorption:
-// 1e-18 .. 1e18) -- an entry of K that underflows is one whose mass is below e^-87 of a unit AT the current potentials, which the
-// log-space sum drops in the same way; and it is recomputed at the next absorption.  The potentials start at u = -(row maximum),
-// v = 0, so that no entry of K overflows whatever the size of the scores (the hand-built scene weights reach +-1000).  A failed
-// check restarts the whole loop with J = 1 (absorb after every iteration), then in log space -- same launch, wave-uniform decision.
-// Layout: lane = row (RB rows per lane), its K row in NC registers.  The column sums are one TRANSPOSING reduction (sk_wave.h): a
-// level combines two registers into one -- the lanes whose level bit is clear keep the first column and receive the partner
-// lane's share of it, the others the second -- so 32 columns cost 16 + 8 + 4 + 2 + 1 exchanges, not 32 x 6, and end with column
-// c's total in lane sk_lane(c): b is ONE register (lane = column), one reciprocal per iteration; the row sums read it back
-// through v_readlane.
-template <int RB, int NC>
-__global__ __launch_bounds__(64) void sinkhorn_wave_kernel(const float* __restrict__ scores, int lds, int m, int n, float alpha, int iters,
-                                                           float* __restrict__ out, const int* __restrict__ n_dev,
-                                                           const unsigned* __restrict__ err, unsigned* lost_count, int first_mode) {
-    constexpr int P = NC <= 8 ? 8 : NC <= 16 ? 16 : 32;
-    if (n_dev) n = *n_dev;
-    const int lane = threadIdx.x, M1 = m + 1, N1 = n + 1;
-    const float inv = 1.0f / ((float)m + (float)n);          // exp(norm)
-    const float norm = -logf((float)m + (float)n);
-    float z[RB][NC], rho[RB], mu[RB], u[RB], vc[NC];
-#pragma unroll
-    for (int j = 0; j < RB; j++) {
-        const int r = lane + 64 * j;
-        const bool valid = r < M1;
-        rho[j] = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            z[j][c] = (valid && c < N1) ? ((r < m && c < n) ? scores[(size_t)r * lds + c] : alpha) : -INFINITY;
-            rho[j] = fmaxf(rho[j], z[j][c]);
-        }
-        mu[j] = valid ? (r < m ? inv : (float)n * inv) : 0.0f;
-    }
-    const int cl = sk_lane(lane & 31) & (P - 1);             // the column whose total this lane receives
-    const float nu = cl < n ? inv : (cl == n ? (float)m * inv : 0.0f);
-    auto bcast = [&](float x, float (&o)[NC]) {             // lane = column -> every lane holds all columns
-#pragma unroll
-        for (int c = 0; c < NC; c++) o[c] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), sk_lane(c)));
-    };
-    bool done = false;
-    for (int mode = first_mode; mode < 2 && !done; mode++) {
-        const int J = mode == 0 ? 10 : 1;
-        float K[RB][NC], a[RB], vl = 0.0f, b = nu != 0.0f ? 1.0f : 0.0f;
-        bool good = true;
-#pragma unroll
-        for (int j = 0; j < RB; j++) {
-            u[j] = mu[j] != 0.0f ? -rho[j] : 0.0f;
-            a[j] = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NC; c++) K[j][c] = expf(z[j][c] + u[j]);          // exp(-inf) = 0 outside the matrix
-        }
-        for (int it0 = 0; it0 < iters; it0 += J) {
-            const int ne = iters - it0 < J ? iters - it0 : J;
-            for (int e = 0; e < ne; e++) {
-                float bc[NC];
-                bcast(b, bc);
-#pragma unroll
-                for (int j = 0; j < RB; j++) {
-                    float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-                    for (int c = 0; c < NC; c += 2) { s0 = fmaf(K[j][c], bc[c], s0); s1 = fmaf(K[j][c + 1], bc[c + 1], s1); }
-                    a[j] = mu[j] != 0.0f ? mu[j] * __builtin_amdgcn_rcpf(s0 + s1) : 0.0f;
-                }
-                float t[32];
-#pragma unroll
-                for (int c = 0; c < 32; c++) {
-                    if (c < NC) {
-                        t[c] = K[0][c] * a[0];
-#pragma unroll
-                        for (int j = 1; j < RB; j++) t[c] = fmaf(K[j][c], a[j], t[c]);
-                    } else t[c] = 0.0f;
-                }
-                const float tot = sk_colsum<P>(t, lane);
-                b = nu != 0.0f ? nu * __builtin_amdgcn_rcpf(tot) : 0.0f;
-            }
-            // absorb the factors into the potentials
-            good = good && (nu == 0.0f || (b > 1e-18f && b < 1e18f));
-            vl += nu != 0.0f ? logf(b) : 0.0f;
-#pragma unroll
-            for (int j = 0; j < RB; j++) {
-                good = good && (mu[j] == 0.0f || (a[j] > 1e-18f && a[j] < 1e18f));
-                u[j] += mu[j] != 0.0f ? logf(a[j]) : 0.0f;
-            }
-            if (it0 + J < iters) {
-                bcast(vl, vc);
-#pragma unroll
-                for (int j = 0; j < RB; j++)
-#pragma unroll
-                    for (int c = 0; c < NC; c++) K[j][c] = expf(z[j][c] + u[j] + vc[c]);
-                b = nu != 0.0f ? 1.0f : 0.0f;
-            }
-        }
-        bcast(vl, vc);
-        done = __all(good);
-    }
-    if (!done) {
-        // log space with the same layout: a row's logsumexp is per lane, a column's a 64-lane reduction
-        const float log_mu_last = logf((float)n) + norm, log_nu_last = logf((float)m) + norm;
-#pragma unroll
-        for (int c = 0; c < NC; c++) vc[c] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < RB; j++) u[j] = 0.0f;
-        for (int it = 0; it < iters; ++it) {
-#pragma unroll
-            for (int j = 0; j < RB; j++) {
-                const int r = lane + 64 * j;
-                float mx = -INFINITY, sum = 0.0f;
-#pragma unroll
-                for (int c = 0; c < NC; c++) mx = fmaxf(mx, z[j][c] + vc[c]);
-#pragma unroll
-                for (int c = 0; c < NC; c++) sum += expf(z[j][c] + vc[c] - mx);          // exp(-inf) = 0 outside the matrix
-                u[j] = r < M1 ? ((r < m) ? norm : log_mu_last) - (logf(sum) + mx) : 0.0f;
-            }
-#pragma unroll
-            for (int c = 0; c < NC; c++) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int j = 0; j < RB; j++) mx = fmaxf(mx, z[j][c] + u[j]);
-                mx = sk_wave_max(mx);
-                float sum = 0.0f;
-#pragma unroll
-                for (int j = 0; j < RB; j++) sum += expf(z[j][c] + u[j] - mx);
-                sum = sk_wave_sum(sum);
-                vc[c] = c < N1 ? ((c < n) ? norm : log_nu_last) - (logf(sum) + mx) : 0.0f;
-            }
-        }
-    }
-    const bool lost = err && *err;
-#pragma unroll
-    for (int j = 0; j < RB; j++) {
-        const int r = lane + 64 * j;
-        if (r < M1) {
-#pragma unroll
-            for (int c = 0; c < NC; c++)
-                if (c < N1) out[(size_t)r * N1 + c] = lost ? NAN : z[j][c] + u[j] + vc[c] - norm;
-        }
-    }
-    if (lane == 0 && lost && lost_count) __hip_atomic_fetch_add(lost_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // err = the persistent matching kernel's flag word (bar + 1): that launch is over (stream order) and its flag has been read
-    // above -- leave generation, flag, the group counters and the per-XCD counters at zero for the next launch (saves a memset per frame)
-    if (err && lane <= 2 * PG_GROUPS + PG_GROUPS) {
-        unsigned* bar = const_cast<unsigned*>(err) - 1;
-        if (lane == 0) { bar[0] = 0u; bar[1] = 0u; }
-        else if (lane <= 2 * PG_GROUPS) bar[32 * lane] = 0u;
-        else bar[32 * (1 + 2 * PG_GROUPS) + (lane - 2 * PG_GROUPS - 1)] = 0u;      // the placement words of gnn_rowpart_kernel
-    }
-}
-
-// log_optimal_transport on the device: the 31-column kernel where it applies, the general one otherwise
-static int launch_sinkhorn(const float* scores, int lds_, int m_, int n_, int n_cap, float alpha, int iters, float* Z_out,
-                           const int* n_dev, hipStream_t st, const unsigned* err = nullptr, unsigned* lost_count = nullptr, bool* cleans_bar = nullptr) {
-    if (n_cap + 1 <= 32 && m_ + 1 <= 128 && odam_cfg::get(odam_cfg::ASSOC_SK_FAST) != 0) {       // one wavefront, registers only
-        const int nc = (n_cap + 1 + 7) >> 3;
-#define ODAM_SKW(RB, NC) hipLaunchKernelGGL((sinkhorn_wave_kernel<RB, NC>), dim3(1), dim3(64), 0, st, scores, lds_, m_, n_, alpha, iters, Z_out, n_dev, err, lost_count, odam_cfg::get(odam_cfg::ASSOC_SK_FAST) - 1)
-        if (m_ + 1 <= 64) { if (nc == 1) ODAM_SKW(1, 8); else if (nc == 2) ODAM_SKW(1, 16); else if (nc == 3) ODAM_SKW(1, 24); else ODAM_SKW(1, 32); }
-        else { if (nc == 1) ODAM_SKW(2, 8); else if (nc == 2) ODAM_SKW(2, 16); else if (nc == 3) ODAM_SKW(2, 24); else ODAM_SKW(2, 32); }
-#undef ODAM_SKW
-        if (cleans_bar) *cleans_bar = err != nullptr;
-    } else if (n_cap + 1 <= 32 && m_ + 1 <= 1100) {        // 1100 rows of 33 floats + u + v fit the 150 KB of dynamic LDS
-        const size_t lds = ((size_t)(m_ + 1) * 33 + (m_ + 1) + 32) * sizeof(float);
-        hipLaunchKernelGGL(sinkhorn32_kernel, dim3(1), dim3(SK_NT), lds, st, scores, lds_, m_, n_, alpha, iters, Z_out, n_dev, err, lost_count);
-    } else {
-        const size_t lds = ((size_t)(m_ + 1) * (n_cap + 1) + (m_ + 1) + (n_cap + 1)) * sizeof(float);
-        hipLaunchKernelGGL(sinkhorn_kernel, dim3(1), dim3(SK_NT), lds, st, scores, lds_, m_, n_, alpha, iters, Z_out, n_dev, err, lost_count);
-    }
-    ODAM_HIP(hipGetLastError());
-    return 0;
 }
 
 int lin(const Lin& L, const float* x, int lda, int M, const float* res, bool relu, float* y, int ldc, const float* scale,
@@ -890,7 +441,7 @@ struct odam_assoc {
     // workspace
     float *feat = nullptr, *h256 = nullptr, *catT = nullptr, *kv = nullptr, *att = nullptr, *h512 = nullptr;
     float *kvX = nullptr, *kvX2 = nullptr, *attX = nullptr, *hX = nullptr;
-    float *catTr = nullptr, *featD = nullptr, *mT = nullptr, *scores = nullptr;
+    float *catTr = nullptr, *mT = nullptr, *scores = nullptr;
     // persistent matching kernel: barrier counters (+ error flag), zeroed on the stream before every launch
     unsigned* bar = nullptr;
     bool persist = true;
@@ -1090,12 +641,10 @@ extern "C" int odam_assoc_finalize(odam_assoc* m) {
     RC(m->alloc(&m->kv, N * 768)); RC(m->alloc(&m->att, N * D)); RC(m->alloc(&m->h512, N * 512));
     // fused tracks [T] and the 30 detection slots share one row block (detections start at row T of the frame) so the
     // shared-weight GNN layers see both sets as ONE matrix
-    RC(m->alloc(&m->catTr, (T + ND) * 512)); RC(m->alloc(&m->featD, ND * FPAD));      // (featD: unused since the detections ride in feat's last 30 rows)
+    RC(m->alloc(&m->catTr, (T + ND) * 512));
     RC(m->alloc(&m->kvX, (T + ND) * 768)); RC(m->alloc(&m->kvX2, (T + ND) * 768)); RC(m->alloc(&m->attX, (T + ND) * D));
     RC(m->alloc(&m->hX, (T + ND) * 512));
     RC(m->alloc(&m->mT, (T + ND + 2) * D)); RC(m->alloc(&m->scores, T * 32));   // the score block reads 32 detection rows
-    ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     {
         float* b = nullptr;
         RC(m->alloc(&b, PG_BAR_WORDS));
@@ -1131,8 +680,8 @@ extern "C" int odam_assoc_finalize(odam_assoc* m) {
 }
 
 // the launch sequence of one forward: ~65 kernels, every one a memory round trip long at these sizes (<= 70 rows)
-static int enqueue_forward(odam_assoc* m, const float* tracks, int T, const float* detections, int n_det, const int* n_dev,
-                           float* Z_out, hipStream_t st, bool allow_persist = true) {
+static int enqueue_forward(odam_assoc* m, const float* tracks, int T, const float* detections, int n_det, float* Z_out, hipStream_t st,
+                           bool allow_persist = true) {
     const int N = T * NT;
     // encoder + frame-index encoding (associator.py:222-229)
     float* X = m->catTr;                      // [T + 30][512]: fused tracks, then the detection slots (rows T ..)
@@ -1154,7 +703,8 @@ static int enqueue_forward(odam_assoc* m, const float* tracks, int T, const floa
     // go through the same weights, so every projection / MLP runs once on the [T + 30] row block; only the attention
     // differs per side (self: own set, cross: the other set).  All deltas come from the layer's inputs: the query,
     // key and value projections are taken before the residual update of either set.
-    if (m->persist && allow_persist && !n_dev) {
+    const bool persist = m->persist && allow_persist;
+    if (persist) {
         GnnArgs g{};
         for (size_t i = 0; i < m->gnn.size(); i++) {
             const Prop& P = m->gnn[i];
@@ -1167,53 +717,46 @@ static int enqueue_forward(odam_assoc* m, const float* tracks, int T, const floa
         g.bar = m->bar; g.timeout_ticks = m->timeout_ticks;
         g.stamps = m->want_stamps ? m->stamps : nullptr;
         g.fake_misplaced = m->fake_misplaced ? 1 : 0;
-        g.merged = m->merged ? 1 : 0;
         // counters and the error flag start from zero every launch: zeroed here, unless the Sinkhorn kernel behind the previous launch did it
         if (!m->bar_clean) ODAM_HIP(hipMemsetAsync(m->bar, 0, sizeof(unsigned) * PG_BAR_WORDS, st));
         m->bar_clean = false;
+        static void (*const kernels[2][2])(GnnArgs) = {{gnn_persistent_kernel<false>, gnn_rowpart_kernel<false>},      // [merged][rowpart]
+                                                       {gnn_persistent_kernel<true>, gnn_rowpart_kernel<true>}};
         const bool rowpart = odam_cfg::get(odam_cfg::ASSOC_PERSIST) == 2;
-        if (m->merged) {
-            if (rowpart) hipLaunchKernelGGL(gnn_rowpart_kernel<true>, dim3(PG_WG), dim3(PG_NT), 0, st, g);
-            else hipLaunchKernelGGL(gnn_persistent_kernel<true>, dim3(PG_WG), dim3(PG_NT), 0, st, g);
-        } else {
-            if (rowpart) hipLaunchKernelGGL(gnn_rowpart_kernel<false>, dim3(PG_WG), dim3(PG_NT), 0, st, g);
-            else hipLaunchKernelGGL(gnn_persistent_kernel<false>, dim3(PG_WG), dim3(PG_NT), 0, st, g);
-        }
+        hipLaunchKernelGGL(kernels[m->merged][rowpart], dim3(PG_WG), dim3(PG_NT), 0, st, g);
         ODAM_HIP(hipGetLastError());
-        // The score matrix keeps its own launch on the tiles of conv_gemm.hip: with saturated scores (the hand-built scene
-        // weights reach +-1000) the Sinkhorn loop shares a detection's mass equally among several tracks and which of them
-        // the Hungarian step then picks hangs on the last bit of the scores -- the reference-run fixtures (tests/test_e2e.py)
-        // hold for the summation order of that kernel, and a different order moved 20 of 40 frames' tie-breaks.
-        const float* mD = m->mT + (size_t)T * D;
-        Lin sc; sc.w = const_cast<float*>(mD); sc.b = nullptr; sc.K = D; sc.N = ND;
-        RC(lin(sc, m->mT, D, T, nullptr, false, m->scores, 32, m->sc16, st));
-        bool cleaned = false;
-        const int rc = launch_sinkhorn(m->scores, 32, T, n_det, n_det, m->bin_score, m->iters, Z_out, nullptr, st, m->bar + 1, m->lost_count, &cleaned);
-        m->bar_clean = rc == 0 && cleaned;
-        return rc;
+    } else {
+        for (size_t i = 0; i < m->gnn.size(); i++) {
+            const Prop& P = m->gnn[i];
+            const bool cross = m->gnn_cross[i] != 0;
+            RC(lin(P.qkv, X, 512, MX, nullptr, false, m->kvX, 3 * D, nullptr, st));     // rows: q | k | v
+            const float* srcT = cross ? m->kvX + (size_t)T * 3 * D : m->kvX;     // source rows of the track queries
+            const float* srcD = cross ? m->kvX : m->kvX + (size_t)T * 3 * D;     // ... of the detection queries
+            const int nT = cross ? ND : T, nD = cross ? T : ND;
+            float* attO = m->merged ? X + D : m->attX;
+            const int ldO = m->merged ? 512 : D;
+            RC(odam_dk::launch_attention_d64(m->kvX, 3 * D, srcT + D, 3 * D, srcT + 2 * D, 3 * D, attO, ldO, 1, 4, T, nT, st));
+            RC(odam_dk::launch_attention_d64(m->kvX + (size_t)T * 3 * D, 3 * D, srcD + D, 3 * D, srcD + 2 * D, 3 * D,
+                                             attO + (size_t)T * ldO, ldO, 1, 4, ND, nD, st));
+            if (!m->merged) RC(lin(P.merge, m->attX, D, MX, nullptr, false, X + D, 512, nullptr, st));
+            RC(lin(P.m0, X, 512, MX, nullptr, true, m->hX, 2 * D, nullptr, st));
+            RC(lin(P.m2, m->hX, 2 * D, MX, X, false, X, 512, nullptr, st));
+        }
+        RC(lin(m->final_proj, X, 512, MX, nullptr, false, m->mT, D, nullptr, st));      // descriptors (associator.py:242-244)
     }
-    for (size_t i = 0; i < m->gnn.size(); i++) {
-        const Prop& P = m->gnn[i];
-        const bool cross = m->gnn_cross[i] != 0;
-        RC(lin(P.qkv, X, 512, MX, nullptr, false, m->kvX, 3 * D, nullptr, st));     // rows: q | k | v
-        const float* srcT = cross ? m->kvX + (size_t)T * 3 * D : m->kvX;     // source rows of the track queries
-        const float* srcD = cross ? m->kvX : m->kvX + (size_t)T * 3 * D;     // ... of the detection queries
-        const int nT = cross ? ND : T, nD = cross ? T : ND;
-        float* attO = m->merged ? X + D : m->attX;
-        const int ldO = m->merged ? 512 : D;
-        RC(odam_dk::launch_attention_d64(m->kvX, 3 * D, srcT + D, 3 * D, srcT + 2 * D, 3 * D, attO, ldO, 1, 4, T, nT, st));
-        RC(odam_dk::launch_attention_d64(m->kvX + (size_t)T * 3 * D, 3 * D, srcD + D, 3 * D, srcD + 2 * D, 3 * D,
-                                         attO + (size_t)T * ldO, ldO, 1, 4, ND, nD, st));
-        if (!m->merged) RC(lin(P.merge, m->attX, D, MX, nullptr, false, X + D, 512, nullptr, st));
-        RC(lin(P.m0, X, 512, MX, nullptr, true, m->hX, 2 * D, nullptr, st));
-        RC(lin(P.m2, m->hX, 2 * D, MX, X, false, X, 512, nullptr, st));
-    }
-    // descriptors, scores, optimal transport (associator.py:242-254)
-    RC(lin(m->final_proj, X, 512, MX, nullptr, false, m->mT, D, nullptr, st));
+    // scores, optimal transport (associator.py:245-254).  Beside the persistent kernel too, the score matrix keeps its own launch on
+    // the tiles of conv_gemm.hip: with saturated scores (the hand-built scene weights reach +-1000) the Sinkhorn loop shares a
+    // detection's mass equally among several tracks and which of them the Hungarian step then picks hangs on the last bit of the
+    // scores -- the reference-run fixtures (tests/test_e2e.py) hold for the summation order of that kernel, and a different order
+    // moved 20 of 40 frames' tie-breaks.
     const float* mD = m->mT + (size_t)T * D;
     Lin sc; sc.w = const_cast<float*>(mD); sc.b = nullptr; sc.K = D; sc.N = ND;
     RC(lin(sc, m->mT, D, T, nullptr, false, m->scores, 32, m->sc16, st));
-    return launch_sinkhorn(m->scores, 32, T, n_det, n_det, m->bin_score, m->iters, Z_out, n_dev, st);   // n_dev (graph replay): n_det is the capacity, 30
+    if (!persist) return launch_sinkhorn(m->scores, 32, T, n_det, n_det, m->bin_score, m->iters, Z_out, nullptr, st);
+    bool cleaned = false;      // the persistent launch's error flag goes along: a lost launch turns Z into NaN
+    const int rc = launch_sinkhorn(m->scores, 32, T, n_det, n_det, m->bin_score, m->iters, Z_out, nullptr, st, m->bar + 1, m->lost_count, &cleaned);
+    m->bar_clean = rc == 0 && cleaned;
+    return rc;
 }
 
 // One frame (stream-ordered).  (Replaying the launch sequence from a hipGraph per track count was built in round 2 and measured
@@ -1223,7 +766,7 @@ extern "C" int odam_assoc_forward(odam_assoc* m, const float* tracks, int T, con
     if (!m || !tracks || !detections || !Z_out) return odam_fail(1, "odam_assoc_forward: null pointer");
     if (!m->finalized) return odam_fail(1, "odam_assoc_forward: call odam_assoc_finalize first");
     if (T < 1 || T > m->max_tracks || n_det < 1 || n_det > ND) return odam_fail(3, "odam_assoc_forward: T / n_det out of range");
-    return enqueue_forward(m, tracks, T, detections, n_det, nullptr, Z_out, (hipStream_t)stream);
+    return enqueue_forward(m, tracks, T, detections, n_det, Z_out, (hipStream_t)stream);
 }
 
 // The same forward with the matching layers as separate launches (no device-wide barrier, no residency assumption): what
@@ -1233,7 +776,7 @@ extern "C" int odam_assoc_forward_sequence(odam_assoc* m, const float* tracks, i
     if (!m || !tracks || !detections || !Z_out) return odam_fail(1, "odam_assoc_forward_sequence: null pointer");
     if (!m->finalized) return odam_fail(1, "odam_assoc_forward_sequence: call odam_assoc_finalize first");
     if (T < 1 || T > m->max_tracks || n_det < 1 || n_det > ND) return odam_fail(3, "odam_assoc_forward_sequence: T / n_det out of range");
-    return enqueue_forward(m, tracks, T, detections, n_det, nullptr, Z_out, (hipStream_t)stream, false);
+    return enqueue_forward(m, tracks, T, detections, n_det, Z_out, (hipStream_t)stream, false);
 }
 
 extern "C" int odam_assoc_lost_launches(odam_assoc* m, unsigned* count) {
@@ -1268,337 +811,6 @@ extern "C" int odam_assoc_set_barrier_timeout_us(odam_assoc* m, long long us) {
     return 0;
 }
 
-// ---- device-resident track windows (OdamProcess._preprocess_tracks, src/processor.py:133-170) --------------------------------
-// Every frame the reference rebuilds, on the host, the associator's track input [T, 79, 100]: the last 100 observations of every
-// live track moved into the CURRENT camera frame (centre through inv(T_wc), azimuth relative to the camera's, the box replaced
-// by the projected extent of the fitted surface).  At 40 tracks that is a 1.3 MB tensor built in numpy and uploaded per frame.
-// Here the observations stay on the device in the WORLD frame (append-only ring per track: 14 float64 per observation), and one
-// launch builds the tensor from them: the same float64 arithmetic per value, rounded to float32 once.
-struct odam_trackwin {
-    int max_tracks = 0, window = 0;
-    double* rows = nullptr;     // [max_tracks][window][14]: frame id, class, bbox px x4, dims x3, t_wo x3, az_wo, score
-    int* count = nullptr;       // [max_tracks] observations appended so far
-    double* stage = nullptr;    // pinned [8][32][14 + 1]: rows + track id of one append
-    double* d_stage = nullptr;  // (unused since the append kernel reads the pinned slot itself; still allocated)
-    double* d_cam = nullptr;    // [16] (unused since the camera travels in the kernel arguments; kept so the handle layout of create / destroy stays as tested)
-    double* h_load = nullptr;   // pinned [max_tracks][window][14]: what odam_trackwin_load's kernel reads (mapped host memory; allocated once -- the
-    int* h_load_meta = nullptr; // load path has no allocation, no hipFree (it waits for every stream of the device) and no copy command)
-    unsigned slot = 0;
-    hipEvent_t copied[8] = {};  // recorded behind the upload from pinned slot i: the host rewrites a slot only after its copy has run
-    bool copied_armed[8] = {};
-    // host side of OdamProcess._prepare_tracks (src/processor.py:172-180): what the surface of a track is evaluated from -- the
-    // means of all its observations' centre, azimuth and dimensions -- kept as running sums, extended by every append
-    struct Sums { long n = 0; double st[3] = {0, 0, 0}, sd[3] = {0, 0, 0}; std::vector<double> az; };
-    std::vector<Sums> sums;
-    bool sums_ok = true;        // false once an append skipped ids or a load came without the full columns
-    float* h_params = nullptr;  // pinned [8][max_tracks][9]
-    float* d_params = nullptr;  // [max_tracks][9] (unused since the surface kernel reads the pinned rows itself; still allocated)
-    double* d_proj = nullptr;   // [max_tracks][4]
-    hipEvent_t params_copied[8] = {};
-    bool params_armed[8] = {};
-    unsigned params_slot = 0;
-};
-
-namespace {
-constexpr int TW_COLS = 14;
-__global__ void trackwin_append_kernel(const double* __restrict__ st, int n, double* __restrict__ rows, int* __restrict__ count, int window) {
-    const int i = blockIdx.x;
-    if (i >= n) return;
-    const int tid_ = (int)st[i * (TW_COLS + 1) + TW_COLS];
-    const int c = count[tid_];      // one block per observation; observations of one append go to different tracks
-    if (threadIdx.x < TW_COLS) rows[((size_t)tid_ * window + (c % window)) * TW_COLS + threadIdx.x] = st[i * (TW_COLS + 1) + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) count[tid_] = c + 1;
-}
-
-// track t: its last k = min(c, window) observations to the ring positions an append sequence of c rows would have left them in
-__global__ __launch_bounds__(128) void trackwin_load_kernel(const double* __restrict__ src, const int* __restrict__ meta, int T,
-                                                            double* __restrict__ rows, int* __restrict__ count, int window) {
-    const int t = blockIdx.x, l = threadIdx.x;
-    const int first = meta[t], c = meta[T + t], k = c < window ? c : window;
-    if (l < k) {
-        const double* r = src + (size_t)(first + l) * TW_COLS;
-        double* o = rows + ((size_t)t * window + ((c - k + l) % window)) * TW_COLS;
-#pragma unroll
-        for (int j = 0; j < TW_COLS; j++) o[j] = r[j];
-    }
-    if (l == 0) count[t] = c;
-}
-
-// out [T][79][window] float32; cam: T_cw rows 0..2 (12), cam_azi, img_w, img_h
-struct Cam15 { double v[15]; };      // travels in the kernel arguments
-__global__ __launch_bounds__(128) void trackwin_build_kernel(const double* __restrict__ rows, const int* __restrict__ count, int window,
-                                                             const double* __restrict__ proj_px, const Cam15 camv,
-                                                             float* __restrict__ out) {
-    const double* cam = camv.v;
-    const int t = blockIdx.x, l = threadIdx.x;
-    if (l >= window) return;
-    const int c = count[t], k = c < window ? c : window;
-    float* o = out + (size_t)t * 79 * window + l;
-    if (l >= k) {
-#pragma unroll 1
-        for (int ch = 0; ch < 79; ch++) o[(size_t)ch * window] = -1.0f;
-        return;
-    }
-    const double* r = rows + ((size_t)t * window + ((c - k + l) % window)) * TW_COLS;
-    const double iw = cam[13], ih = cam[14];
-    auto clip = [](double x) { return x < -1.0 ? -1.0 : (x > 2.0 ? 2.0 : x); };
-    double v[15];
-    v[0] = r[0]; v[1] = r[1];
-    v[2] = clip(proj_px[t * 4 + 0] / iw); v[3] = clip(proj_px[t * 4 + 1] / ih);
-    v[4] = clip(proj_px[t * 4 + 2] / iw); v[5] = clip(proj_px[t * 4 + 3] / ih);
-    v[6] = r[6]; v[7] = r[7]; v[8] = r[8];
-    const double x = r[9], y = r[10], z = r[11];
-    v[9] = x * cam[0] + y * cam[1] + z * cam[2] + cam[3];
-    v[10] = x * cam[4] + y * cam[5] + z * cam[6] + cam[7];
-    v[11] = x * cam[8] + y * cam[9] + z * cam[10] + cam[11];
-    const double rel = r[12] - cam[12];
-    v[12] = sin(rel); v[13] = cos(rel);
-    v[14] = r[13];
-#pragma unroll
-    for (int ch = 0; ch < 15; ch++) o[(size_t)ch * window] = (float)v[ch];
-#pragma unroll 1
-    for (int ch = 15; ch < 79; ch++) o[(size_t)ch * window] = -1.0f;
-}
-}  // namespace
-
-extern "C" int odam_trackwin_create(int max_tracks, int window, odam_trackwin** out) {
-    if (!out || max_tracks < 1 || max_tracks > 4096 || window < 1 || window > 128) return odam_fail(1, "odam_trackwin_create: bad argument");
-    odam_trackwin* w = new odam_trackwin();
-    w->max_tracks = max_tracks; w->window = window;
-    if (hipMalloc((void**)&w->rows, sizeof(double) * (size_t)max_tracks * window * TW_COLS) != hipSuccess ||
-        hipMalloc((void**)&w->count, sizeof(int) * (size_t)max_tracks) != hipSuccess ||
-        hipMalloc((void**)&w->d_stage, sizeof(double) * 32 * (TW_COLS + 1)) != hipSuccess ||
-        hipMalloc((void**)&w->d_cam, sizeof(double) * 16) != hipSuccess ||
-        hipHostMalloc((void**)&w->h_load, sizeof(double) * (size_t)max_tracks * window * TW_COLS, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&w->h_load_meta, sizeof(int) * 2 * (size_t)max_tracks, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&w->stage, sizeof(double) * 8 * 32 * (TW_COLS + 1), hipHostMallocDefault) != hipSuccess) {
-        if (w->rows) (void)hipFree(w->rows);
-        if (w->count) (void)hipFree(w->count);
-        if (w->d_stage) (void)hipFree(w->d_stage);
-        if (w->d_cam) (void)hipFree(w->d_cam);
-        if (w->h_load) (void)hipHostFree(w->h_load);
-        if (w->h_load_meta) (void)hipHostFree(w->h_load_meta);
-        if (w->stage) (void)hipHostFree(w->stage);
-        delete w;
-        return odam_fail(2, "odam_trackwin_create: allocation failed");
-    }
-    // counts start at zero, and are zero when this call returns: through a private non-blocking stream -- hipMemset would be
-    // ordered on the NULL stream, may still be pending when it returns and then land behind a load / append the caller issues on
-    // a stream of its own (it did: the counts of a freshly loaded store went back to zero -- GPU test
-    // test_stores_created_while_the_default_stream_is_busy); waiting for the NULL stream instead would wait for whatever another
-    // thread has queued there
-    {
-        hipStream_t init = nullptr;
-        const bool ok = hipStreamCreateWithFlags(&init, hipStreamNonBlocking) == hipSuccess &&
-                        hipMemsetAsync(w->count, 0, sizeof(int) * (size_t)max_tracks, init) == hipSuccess &&
-                        hipStreamSynchronize(init) == hipSuccess;
-        if (init) (void)hipStreamDestroy(init);
-        if (!ok) {
-            (void)hipFree(w->rows); (void)hipFree(w->count); (void)hipFree(w->d_stage); (void)hipFree(w->d_cam); (void)hipHostFree(w->h_load); (void)hipHostFree(w->h_load_meta); (void)hipHostFree(w->stage);
-            delete w;
-            return odam_fail(2, "odam_trackwin_create: initialisation failed");
-        }
-    }
-    for (int i = 0; i < 8; i++)
-        if (hipEventCreateWithFlags(&w->copied[i], hipEventDisableTiming) != hipSuccess) {
-            for (int j = 0; j < i; j++) (void)hipEventDestroy(w->copied[j]);
-            (void)hipFree(w->rows); (void)hipFree(w->count); (void)hipFree(w->d_stage); (void)hipFree(w->d_cam); (void)hipHostFree(w->h_load); (void)hipHostFree(w->h_load_meta); (void)hipHostFree(w->stage);
-            delete w;
-            return odam_fail(2, "odam_trackwin_create: event creation failed");
-        }
-    *out = w;
-    return 0;
-}
-
-extern "C" int odam_trackwin_destroy(odam_trackwin* w) {
-    if (!w) return 0;
-    for (int i = 0; i < 8; i++) {
-        if (w->params_armed[i]) (void)hipEventSynchronize(w->params_copied[i]);
-        if (w->params_copied[i]) (void)hipEventDestroy(w->params_copied[i]);
-    }
-    if (w->h_params) (void)hipHostFree(w->h_params);
-    if (w->d_params) (void)hipFree(w->d_params);
-    if (w->d_proj) (void)hipFree(w->d_proj);
-    for (int i = 0; i < 8; i++) {
-        if (w->copied_armed[i]) (void)hipEventSynchronize(w->copied[i]);      // no upload may still be reading the pinned ring
-        (void)hipEventDestroy(w->copied[i]);
-    }
-    (void)hipFree(w->rows); (void)hipFree(w->count); (void)hipFree(w->d_stage); (void)hipFree(w->d_cam); (void)hipHostFree(w->h_load); (void)hipHostFree(w->h_load_meta); (void)hipHostFree(w->stage);
-    delete w;
-    return 0;
-}
-
-extern "C" int odam_trackwin_reset(odam_trackwin* w, void* stream) {
-    if (!w) return odam_fail(1, "odam_trackwin_reset: null handle");
-    ODAM_HIP(hipMemsetAsync(w->count, 0, sizeof(int) * (size_t)w->max_tracks, (hipStream_t)stream));
-    w->sums.clear(); w->sums_ok = true;
-    return 0;
-}
-
-extern "C" int odam_trackwin_append(odam_trackwin* w, int n, const int* track_ids, const double* rows14, void* stream) {
-    if (!w || n < 0 || n > 32 || (n && (!track_ids || !rows14))) return odam_fail(1, "odam_trackwin_append: bad argument (at most 32 observations per call)");
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    for (int i = 0; i < n; i++)
-        if (track_ids[i] < 0 || track_ids[i] >= w->max_tracks) return odam_fail(3, "odam_trackwin_append: track id outside the handle's capacity");
-    // The ring slot may be rewritten only once the kernel that read it eight appends ago has run -- appends can queue behind long
-    // kernels on the stream (a detector forward, a rebuild).
-    const int si = (int)(w->slot++ & 7);
-    if (w->copied_armed[si]) ODAM_HIP(hipEventSynchronize(w->copied[si]));
-    double* slot = w->stage + (size_t)si * 32 * (TW_COLS + 1);
-    for (int i = 0; i < n; i++) {
-        for (int c = 0; c < TW_COLS; c++) slot[i * (TW_COLS + 1) + c] = rows14[i * TW_COLS + c];
-        slot[i * (TW_COLS + 1) + TW_COLS] = (double)track_ids[i];
-    }
-    // the kernel reads the pinned slot itself (mapped host memory; <= 3.8 KB): no copy command in the frame's chain.  The slot is the
-    // host's again once that kernel has run -- the event behind it is what the next use of the slot waits for.
-    hipLaunchKernelGGL(trackwin_append_kernel, dim3(n), dim3(64), 0, st, slot, n, w->rows, w->count, w->window);
-    ODAM_HIP(hipGetLastError());
-    ODAM_HIP(hipEventRecord(w->copied[si], st));
-    w->copied_armed[si] = true;
-    for (int i = 0; i < n; i++) {
-        const size_t t = (size_t)track_ids[i];
-        if (t > w->sums.size()) w->sums_ok = false;        // a gap in the ids: no sums for the skipped tracks
-        if (t >= w->sums.size()) w->sums.resize(t + 1);
-        odam_trackwin::Sums& q = w->sums[t];
-        const double* r = rows14 + (size_t)i * TW_COLS;
-        q.n++;
-        for (int c = 0; c < 3; c++) { q.sd[c] += r[6 + c]; q.st[c] += r[9 + c]; }      // row after row: numpy's axis-0 reduce of an [n, 3] block
-        q.az.push_back(r[12]);
-    }
-    return 0;
-}
-
-// Bulk (re)build of the mirror: track t gets the last min(lengths[t], window) of its observations -- rows14 holds exactly those,
-// track after track -- and the count lengths[t].  One upload and one launch; synchronises the stream (a rebuild is rare: first
-// use, or the host edited its track list).
-extern "C" int odam_trackwin_load(odam_trackwin* w, int T, const int* lengths, const double* rows14, void* stream) {
-    if (!w || T < 0 || T > w->max_tracks || (T && (!lengths || !rows14))) return odam_fail(1, "odam_trackwin_load: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    ODAM_HIP(hipMemsetAsync(w->count, 0, sizeof(int) * (size_t)w->max_tracks, st));
-    w->sums.clear(); w->sums_ok = T == 0;
-    if (T == 0) return 0;
-    std::vector<int> meta(2 * (size_t)T);      // [t] = first row of track t in rows14, [T + t] = its length
-    long total = 0;
-    for (int t = 0; t < T; t++) {
-        if (lengths[t] < 0) return odam_fail(1, "odam_trackwin_load: negative track length");
-        meta[t] = (int)total; meta[T + t] = lengths[t];
-        total += lengths[t] < w->window ? lengths[t] : w->window;
-    }
-    // The kernel reads the handle's pinned staging itself (mapped host memory, sized for max_tracks full windows at creation): no
-    // allocation here, no hipFree (it waits for every stream of the device -- for a detector running beside this caller) and no
-    // copy command (free: every load ends with a stream synchronisation, so the staging is the caller's again when this returns).
-    int rc = 0;
-    std::memcpy(w->h_load, rows14, sizeof(double) * (size_t)total * TW_COLS);
-    std::memcpy(w->h_load_meta, meta.data(), sizeof(int) * 2 * (size_t)T);
-    {
-        hipLaunchKernelGGL(trackwin_load_kernel, dim3(T), dim3(128), 0, st, w->h_load, w->h_load_meta, T, w->rows, w->count, w->window);
-        if (hipGetLastError() != hipSuccess) rc = odam_fail(2, "odam_trackwin_load: launch failed");
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = odam_fail(2, "odam_trackwin_load: stream synchronisation failed");
-    return rc;
-}
-
-// np.add.reduce of a 1-D float64 array (numpy/core/src/umath/loops_utils.h.src, pairwise sum, started from the identity):
-// fewer than 8 values one after the other; up to 128 in eight interleaved partial sums combined as a tree, the tail after; longer
-// arrays halved (the first half a multiple of 8) -- tests/test_assoc_gpu.py checks it against numpy bit for bit
-static double np_pairwise(const double* a, size_t n) {
-    if (n < 8) {
-        double r = 0.0;
-        for (size_t i = 0; i < n; i++) r += a[i];
-        return r;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; j++) r[j] = a[j];
-        size_t i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; j++) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) res += a[i];
-        return res;
-    }
-    size_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise(a, n2) + np_pairwise(a + n2, n - n2);
-}
-
-// the sums of a host track list in one go (after odam_trackwin_load): cols7 [host][sum_t lengths[t]][7] = columns 6..12 (dims x3,
-// t_wo x3, az_wo) of EVERY observation of track 0, then of track 1, ...
-extern "C" int odam_trackwin_load_sums(odam_trackwin* w, int T, const int* lengths, const double* cols7) {
-    if (!w || T < 0 || T > w->max_tracks || (T && (!lengths || !cols7))) return odam_fail(1, "odam_trackwin_load_sums: bad argument");
-    w->sums.assign((size_t)T, odam_trackwin::Sums());
-    const double* r = cols7;
-    for (int t = 0; t < T; t++) {
-        odam_trackwin::Sums& q = w->sums[t];
-        if (lengths[t] < 1) return odam_fail(1, "odam_trackwin_load_sums: a track without observations");
-        q.n = lengths[t];
-        q.az.resize((size_t)lengths[t]);
-        for (int i = 0; i < lengths[t]; i++, r += 7) {
-            for (int c = 0; c < 3; c++) { q.sd[c] += r[c]; q.st[c] += r[3 + c]; }
-            q.az[i] = r[6];
-        }
-    }
-    w->sums_ok = true;
-    return 0;
-}
-
-// parameter rows the surfaces of the tracks are evaluated from, as sq.init_params / _prepare_tracks build them (processor.py:172-180):
-// mean centre, mean azimuth, sqrt(max(mean dims, 0.05) / 2), shape exponents -0;  out [host][T][9] float32
-extern "C" int odam_trackwin_params(odam_trackwin* w, int T, float* out) {
-    if (!w || T < 0 || (T && !out)) return odam_fail(1, "odam_trackwin_params: bad argument");
-    if (!w->sums_ok || (size_t)T != w->sums.size()) return odam_fail(4, "odam_trackwin_params: the running sums do not cover these tracks (load them: odam_trackwin_load_sums)");
-    for (int t = 0; t < T; t++) {
-        const odam_trackwin::Sums& q = w->sums[t];
-        const double n = (double)q.n;
-        float* o = out + (size_t)t * 9;
-        for (int c = 0; c < 3; c++) o[c] = (float)(q.st[c] / n);
-        o[3] = (float)((0.0 + np_pairwise(q.az.data(), q.az.size())) / n);
-        for (int c = 0; c < 3; c++) {
-            const double d = q.sd[c] / n;
-            o[4 + c] = (float)std::sqrt((d > 0.05 ? d : 0.05) / 2);       // np.maximum(., 0.05); NaN stays NaN in numpy -- not reachable, dims come from a sigmoid
-        }
-        o[7] = o[8] = -0.0f;
-    }
-    return 0;
-}
-
-// One call for OdamProcess._prepare_tracks: parameter rows (above) -> upload -> odam_sq_project_extents on `sq` -> the window tensor
-// out [dev][T][79][window] for the camera T_cw12_K9 = rows 0..2 of inv(T_wc) (12) + K (9), azimuth cam_azi, image size.  Stream-ordered.
-extern "C" int odam_sq_project_extents(struct odam_sq_ctx* ctx, int n, const float* params, const double* T_cw12_K9, double* out_px, void* stream);
-extern "C" int odam_trackwin_build_tracks(odam_trackwin* w, struct odam_sq_ctx* sq, int T, const double* T_cw12_K9, double cam_azi,
-                                          double img_w, double img_h, float* out, void* stream) {
-    if (!w || !sq || T < 0 || T > w->max_tracks || (T && (!T_cw12_K9 || !out))) return odam_fail(1, "odam_trackwin_build_tracks: bad argument");
-    if (T == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (!w->h_params) {
-        if (hipHostMalloc((void**)&w->h_params, sizeof(float) * 8 * (size_t)w->max_tracks * 9, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc((void**)&w->d_params, sizeof(float) * (size_t)w->max_tracks * 9) != hipSuccess ||
-            hipMalloc((void**)&w->d_proj, sizeof(double) * (size_t)w->max_tracks * 4) != hipSuccess) {
-            if (w->h_params) { (void)hipHostFree(w->h_params); w->h_params = nullptr; }
-            if (w->d_params) { (void)hipFree(w->d_params); w->d_params = nullptr; }
-            return odam_fail(2, "odam_trackwin_build_tracks: allocation failed");
-        }
-        for (int i = 0; i < 8; i++) ODAM_HIP(hipEventCreateWithFlags(&w->params_copied[i], hipEventDisableTiming));
-    }
-    const int si = (int)(w->params_slot++ & 7);
-    if (w->params_armed[si]) ODAM_HIP(hipEventSynchronize(w->params_copied[si]));
-    float* hp = w->h_params + (size_t)si * w->max_tracks * 9;
-    if (int rc = odam_trackwin_params(w, T, hp)) return rc;
-    // the surface kernel reads the pinned rows itself (mapped host memory, 36 bytes per track): no copy command; the slot is free
-    // again when the launches that read it have run
-    if (int rc = odam_sq_project_extents(sq, T, hp, T_cw12_K9, w->d_proj, stream)) return rc;
-    ODAM_HIP(hipEventRecord(w->params_copied[si], st));
-    w->params_armed[si] = true;
-    Cam15 cam;
-    for (int i = 0; i < 12; i++) cam.v[i] = T_cw12_K9[i];
-    cam.v[12] = cam_azi; cam.v[13] = img_w; cam.v[14] = img_h;
-    hipLaunchKernelGGL(trackwin_build_kernel, dim3(T), dim3(128), 0, st, w->rows, w->count, w->window, w->d_proj, cam, out);
-    ODAM_HIP(hipGetLastError());
-    return 0;
-}
-
 // One frame of OdamProcess.process_frame's device work behind ONE call (src/processor.py:320-337): the observations the previous frame
 // attached (n_app <= 30 rows: odam_trackwin_append), this frame's track input for its camera (odam_trackwin_build_tracks) and the
 // association forward on it (odam_assoc_forward) -- the same three entry points in the same order, so the results are theirs bit for
@@ -1613,17 +825,6 @@ extern "C" int odam_assoc_step(odam_assoc* m, odam_trackwin* w, struct odam_sq_c
     if (n_app) { if (int rc = odam_trackwin_append(w, n_app, app_ids, app_rows14, stream)) return rc; }
     if (int rc = odam_trackwin_build_tracks(w, sq, T, T_cw12_K9, cam_azi, img_w, img_h, tracks_out, stream)) return rc;
     return odam_assoc_forward(m, tracks_out, T, detections, n_det, Z_out, stream);
-}
-
-extern "C" int odam_trackwin_build(odam_trackwin* w, int T, const double* proj_px, const double* cam15, float* out, void* stream) {
-    if (!w || T < 0 || T > w->max_tracks || (T && (!proj_px || !cam15 || !out))) return odam_fail(1, "odam_trackwin_build: bad argument");
-    if (T == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    Cam15 cam;
-    for (int i = 0; i < 15; i++) cam.v[i] = cam15[i];
-    hipLaunchKernelGGL(trackwin_build_kernel, dim3(T), dim3(128), 0, st, w->rows, w->count, w->window, proj_px, cam, out);
-    ODAM_HIP(hipGetLastError());
-    return 0;
 }
 
 // diagnostics: run the next forwards with stage stamps (enable != 0), or read the stamps of the last one: out[0..n) =
@@ -1645,241 +846,5 @@ extern "C" int odam_assoc_debug_read(odam_assoc* m, int which, float* out, long 
     const float* src = which == 0 ? m->catTr : (which == 1 ? m->mT : m->scores);
     ODAM_HIP(hipDeviceSynchronize());
     ODAM_HIP(hipMemcpy(out, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int odam_assoc_sinkhorn(const float* scores, int lds_, int m_, int n_, float alpha, int iters, float* Z_out,
-                                   void* stream) {
-    if (!scores || !Z_out || m_ < 1 || n_ < 1 || (size_t)(m_ + 1) * (n_ + 1) > 36000)
-        return odam_fail(1, "odam_assoc_sinkhorn: bad argument");
-    static bool attr = false;
-    if (!attr) {
-        ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr = true;
-    }
-    return launch_sinkhorn(scores, lds_, m_, n_, n_, alpha, iters, Z_out, nullptr, (hipStream_t)stream);
-}
-
-// ---- the Hungarian step (src/models/associator.py:19-35) on the device ------------------------------------------------------------
-// hungarian_matching() hands 1 - exp(Z[:-1, :-1]) to scipy.optimize.linear_sum_assignment and keeps the pairs whose score exceeds the
-// threshold.  scipy's solver is the shortest-augmenting-path algorithm for the rectangular problem (Crouse 2016; scipy/optimize/
-// rectangular_lsap, version 1.6 on -- a published algorithm with a fixed, sequential tie order: columns are scanned in the order of a
-// "remaining" list that starts reversed and shrinks by swap-removal, among equal reduced costs the LAST unassigned column of that scan wins,
-// else the first one).  One wavefront restates it: lanes own columns (two per lane: up to 128), the scan over the remaining columns is one
-// lexicographic reduction on (reduced cost, assigned?, position in the list), duals and costs in binary64 in scipy's order of operations.
-// The result is the same matching whenever the scores are the same floats; the scores themselves are exp() of the device here and torch's
-// CPU exp on the host path (one ulp apart at most: a pair changes only on an exact tie or a score within an ulp of the threshold).
-namespace {
-constexpr int HG_MAXR = 32, HG_MAXC = 128;
-// what lane (l ^ (1 << BIT)) holds, on DPP / v_permlane*_swap (sk_wave.h): bit moves, any payload
-template <int BIT> __device__ __forceinline__ unsigned hg_xor(unsigned v) { return __builtin_bit_cast(unsigned, sk_xor<BIT>(__builtin_bit_cast(float, v))); }
-struct HgKey { double c; unsigned t; };      // reduced cost; tail = not-free << 19 | tie key << 12 | column << 5 | row of the column (if assigned)
-template <int BIT> __device__ __forceinline__ void hg_step(HgKey& b) {
-    const unsigned long long cb = __builtin_bit_cast(unsigned long long, b.c);
-    const unsigned lo = hg_xor<BIT>((unsigned)cb), hi = hg_xor<BIT>((unsigned)(cb >> 32)), ot = hg_xor<BIT>(b.t);
-    const double oc = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-    if (oc < b.c || (oc == b.c && ot < b.t)) { b.c = oc; b.t = ot; }
-}
-__global__ __launch_bounds__(64) void hungarian_wave_kernel(const float* __restrict__ Z, int T, int n_det, int ldz, double thr, int log_domain,
-                                                            int* __restrict__ match_out, int* __restrict__ status) {
-    __shared__ double cost[HG_MAXR * HG_MAXC];
-    __shared__ float sc_[HG_MAXR * HG_MAXC];
-    __shared__ double u[HG_MAXR], spc_l[HG_MAXC];
-    __shared__ int col4row[HG_MAXR], row4col[HG_MAXC], path_l[HG_MAXC], remaining[HG_MAXC];
-    __shared__ unsigned char SR[HG_MAXR];
-    const int lane = threadIdx.x;
-    // ONE wavefront: its LDS operations execute in program order, so a wave-level fence (no s_barrier) orders a lane's write before the others' reads
-    auto sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const bool tr = n_det < T;                       // scipy transposes a tall matrix
-    const int nr = tr ? n_det : T, nc = tr ? T : n_det;
-    // Z may live in pinned HOST memory (the Sinkhorn kernel writes it there): every element is requested once, the requests of a batch of
-    // eight in flight together, and kept in LDS as the score (the threshold test at the end reads it again)
-    const int total = T * n_det;
-    for (int base = 0; base < total; base += 64 * 8) {
-        float z[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int idx = base + k * 64 + lane;
-            const int r = idx / n_det, c = idx - r * n_det;
-            z[k] = idx < total ? Z[(size_t)r * ldz + c] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int idx = base + k * 64 + lane;
-            if (idx < total) {
-                const int r = idx / n_det, c = idx - r * n_det;
-                const float s = log_domain ? expf(z[k]) : z[k];
-                const int i = tr ? c : r, j = tr ? r : c;
-                sc_[i * HG_MAXC + j] = s;
-                cost[i * HG_MAXC + j] = (double)(1.0f - s);      // numpy: float32 (1 - scores), widened by the solver
-            }
-        }
-    }
-    // a lane keeps the state of its two columns (lane, lane + 64) in registers; rows, the scan list and what lane 0's augmentation walks are in LDS
-    const int jc[2] = {lane, lane + 64};
-    const bool has[2] = {jc[0] < nc, jc[1] < nc};
-    double vv[2] = {0.0, 0.0}, spc[2];
-    int r4c[2] = {-1, -1}, pth[2] = {-1, -1}, pos[2];
-    bool SC[2];
-    for (int j = lane; j < nc; j += 64) row4col[j] = -1;
-    if (lane < nr) { u[lane] = 0.0; col4row[lane] = -1; }
-    sync();
-    const double INF = __builtin_huge_val();
-    for (int cur = 0; cur < nr; cur++) {
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            if (has[q]) { remaining[nc - 1 - jc[q]] = jc[q]; r4c[q] = row4col[jc[q]]; }      // list position it holds column nc - it - 1
-            pos[q] = nc - 1 - jc[q]; spc[q] = INF; SC[q] = !has[q];
-        }
-        if (lane < nr) SR[lane] = 0;
-        sync();
-        double minVal = 0.0;
-        int i = cur, num_remaining = nc, sink = -1;
-        while (sink == -1) {
-            if (lane == 0) SR[i] = 1;
-            const double ui = u[i];
-            HgKey best{INF, 0xffffffffu};
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                if (SC[q]) continue;
-                const double r = minVal + cost[i * HG_MAXC + jc[q]] - ui - vv[q];
-                if (r < spc[q]) { pth[q] = i; spc[q] = r; }
-                const bool free_ = r4c[q] == -1;
-                // among equal reduced costs: the LAST free column of the scan (largest list position), else the first assigned one
-                const unsigned t = (free_ ? 0u : 1u << 19) | (unsigned)(free_ ? 127 - pos[q] : pos[q]) << 12 | (unsigned)jc[q] << 5 | (unsigned)(free_ ? 0 : r4c[q]);
-                if (spc[q] < best.c || (spc[q] == best.c && t < best.t)) { best.c = spc[q]; best.t = t; }
-            }
-            hg_step<0>(best); hg_step<1>(best); hg_step<2>(best); hg_step<3>(best); hg_step<4>(best); hg_step<5>(best);
-            minVal = best.c;
-            if (!(minVal < INF)) { if (lane == 0) *status = 1; return; }      // infeasible, or NaN scores (scipy raises)
-            const int j = (best.t >> 5) & 127, kk = (best.t >> 12) & 127;
-            const bool jfree = !(best.t >> 19);
-            const int idx = jfree ? 127 - kk : kk;                             // the winner's position in the list
-            if (jfree) sink = j; else i = best.t & 31;
-            const int last = remaining[num_remaining - 1];
-            sync();
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                if (jc[q] == j) { SC[q] = true; remaining[idx] = last; }
-                if (jc[q] == last) pos[q] = idx;
-            }
-            num_remaining--;
-            sync();
-        }
-        // what the dual update of the rows and lane 0's augmentation read by column index
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-            if (has[q]) { spc_l[jc[q]] = spc[q]; path_l[jc[q]] = pth[q]; if (SC[q]) vv[q] -= minVal - spc[q]; }
-        sync();
-        if (lane < nr && SR[lane] && lane != cur) u[lane] += minVal - spc_l[col4row[lane]];
-        if (lane == 0) u[cur] += minVal;
-        sync();
-        if (lane == 0) {
-            int j = sink;
-            while (true) {
-                const int ii = path_l[j];
-                row4col[j] = ii;
-                const int t = col4row[ii]; col4row[ii] = j; j = t;
-                if (ii == cur) break;
-            }
-        }
-        sync();
-    }
-    for (int c = lane; c < n_det; c += 64) match_out[c] = -1;
-    sync();
-    if (lane < nr) {
-        const int jcol = col4row[lane];
-        if (jcol >= 0) {
-            const int r = tr ? jcol : lane, c = tr ? lane : jcol;
-            if ((double)sc_[lane * HG_MAXC + jcol] > thr) match_out[c] = r;
-        }
-    }
-    if (lane == 0) *status = 0;
-}
-}  // namespace
-
-// ---- the same step on the HOST, with the tests that follow it (OdamProcess's fast path: one call between a frame's result and the next launch) ----
-// scipy.optimize.linear_sum_assignment(1 - scores) as hungarian_matching calls it (associator.py:19-35) -- the sequential form of the solver
-// restated above: rows in order, the scan over a "remaining" list that starts reversed and shrinks by swap-removal, among equal reduced costs a
-// free column wins and the LAST such column of the scan, binary64 duals in scipy's order of operations -- then `score > match_threshold` for
-// the matched pairs and `!(score[pair or dustbin row] < score_threshold)` of _attach_to_tracks (processor.py:228-231), both as numpy / torch
-// compare a float32 array with a Python float: in float32.  No device work.
-extern "C" int odam_assoc_attach(const float* score, int n_tracks, int n_det, int lds, double match_threshold, double score_threshold,
-                                 int* match_out, unsigned char* keep_out) {
-    if (!score || !match_out || !keep_out || n_tracks < 0 || n_det < 0 || lds < n_det + 1) return odam_fail(1, "odam_assoc_attach: bad argument");
-    for (int c = 0; c < n_det; c++) match_out[c] = -1;
-    const bool tr = n_det < n_tracks;                       // scipy transposes a tall matrix
-    const int nr = tr ? n_det : n_tracks, nc = tr ? n_tracks : n_det;
-    if (nr > 0) {
-        std::vector<double> cost((size_t)nr * nc), u(nr, 0.0), v(nc, 0.0), spc(nc);
-        std::vector<int> col4row(nr, -1), row4col(nc, -1), path(nc, -1), remaining(nc);
-        std::vector<unsigned char> SR(nr), SC(nc);
-        for (int r = 0; r < n_tracks; r++)
-            for (int c = 0; c < n_det; c++) {
-                const double x = (double)(1.0f - score[(size_t)r * lds + c]);      // numpy: float32 (1 - scores), widened by the solver
-                if (x != x || x == -__builtin_huge_val()) return odam_fail(4, "odam_assoc_attach: matrix contains invalid numeric entries");
-                cost[tr ? (size_t)c * nc + r : (size_t)r * nc + c] = x;
-            }
-        const double INF = __builtin_huge_val();
-        for (int cur = 0; cur < nr; cur++) {
-            double minVal = 0.0;
-            int num_remaining = nc, sink = -1, i = cur;
-            for (int it = 0; it < nc; it++) remaining[it] = nc - it - 1;
-            std::fill(SR.begin(), SR.end(), 0); std::fill(SC.begin(), SC.end(), 0); std::fill(spc.begin(), spc.end(), INF);
-            while (sink == -1) {
-                int index = -1;
-                double lowest = INF;
-                SR[i] = 1;
-                for (int it = 0; it < num_remaining; it++) {
-                    const int j = remaining[it];
-                    const double r = minVal + cost[(size_t)i * nc + j] - u[i] - v[j];
-                    if (r < spc[j]) { path[j] = i; spc[j] = r; }
-                    if (spc[j] < lowest || (spc[j] == lowest && row4col[j] == -1)) { lowest = spc[j]; index = it; }
-                }
-                minVal = lowest;
-                if (!(minVal < INF)) return odam_fail(5, "odam_assoc_attach: cost matrix is infeasible");
-                const int j = remaining[index];
-                if (row4col[j] == -1) sink = j; else i = row4col[j];
-                SC[j] = 1;
-                remaining[index] = remaining[--num_remaining];
-            }
-            u[cur] += minVal;
-            for (int r = 0; r < nr; r++) if (SR[r] && r != cur) u[r] += minVal - spc[col4row[r]];
-            for (int j = 0; j < nc; j++) if (SC[j]) v[j] -= minVal - spc[j];
-            int j = sink;
-            while (true) {
-                const int ii = path[j];
-                row4col[j] = ii;
-                const int t = col4row[ii]; col4row[ii] = j; j = t;
-                if (ii == cur) break;
-            }
-        }
-        const float mt = (float)match_threshold;
-        for (int r0 = 0; r0 < nr; r0++) {
-            const int r = tr ? col4row[r0] : r0, c = tr ? r0 : col4row[r0];
-            if (score[(size_t)r * lds + c] > mt) match_out[c] = r;
-        }
-    }
-    const float st = (float)score_threshold;
-    for (int c = 0; c < n_det; c++) {
-        const int r = match_out[c] < 0 ? n_tracks : match_out[c];      // index -1 reads the dustbin row, as in the reference
-        keep_out[c] = !(score[(size_t)r * lds + c] < st);
-    }
-    return 0;
-}
-
-extern "C" int odam_assoc_hungarian(const float* Z, int n_tracks, int n_det, int ldz, double threshold, int log_domain, int* match_out,
-                                    int* status, void* stream) {
-    if (!Z || !match_out || !status || n_tracks < 0 || n_det < 0 || ldz < n_det)
-        return odam_fail(1, "odam_assoc_hungarian: bad argument");
-    const int nr = n_det < n_tracks ? n_det : n_tracks, nc = n_det < n_tracks ? n_tracks : n_det;
-    if (nr > HG_MAXR || nc > HG_MAXC) return odam_fail(3, "odam_assoc_hungarian: more than 32 x 128 (the caller solves it on the host)");      // (3 = ODAM_E_LIMIT of odam_sq.h)
-    hipLaunchKernelGGL(hungarian_wave_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, Z, n_tracks, n_det, ldz, threshold, log_domain, match_out, status);
-    ODAM_HIP(hipGetLastError());
     return 0;
 }

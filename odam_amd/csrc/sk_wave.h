@@ -1,4 +1,4 @@
-// sk_wave.h -- cross-lane pieces of the one-wavefront Sinkhorn kernel (assoc.hip: sinkhorn_wave_kernel): exchanges over every lane bit
+// sk_wave.h -- cross-lane pieces of the one-wavefront Sinkhorn kernel (assoc_sinkhorn.hip: sinkhorn_wave_kernel): exchanges over every lane bit
 // of a 64-lane wavefront on DPP / v_permlane*_swap, and the transposing column reduction built from them.
 #pragma once
 #include <hip/hip_runtime.h>
