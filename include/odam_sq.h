@@ -169,6 +169,30 @@ int odam_dq_fit_batch(odam_sq_ctx* ctx, int n_obj, const float* init5, const flo
                       float* out_Q, float* loss_log, float* traj, int* status, void* stream);
 int odam_dq_set_group_waves(odam_sq_ctx* ctx, int waves);
 
+/*
+ * The closed-form dual quadric of an object from the planes through its 2D box edges -- no 3D guess, float64 throughout:
+ *   src/super_quadric/sq_libs.py:30-36           compute_quadric_svd  (A = Sigma^T Sigma, eigenvector of the smallest eigenvalue)
+ *   src/utils/tracking_gt_utils.py:198-205       load_pred_object's plane_vecs: bbox_to_lines, normalize_plane(line @ P), plane_2vect
+ *   src/super_quadric/quadric_helper.py:16-48    quadric_2mat, plane_2vect
+ * ONE launch for all objects, one wavefront per object, views strided over the lanes, odam_dq_set_group_waves objects per
+ * workgroup; stream-ordered, no synchronisation, no allocation.  The accumulation order of A and the Jacobi pivot order are fixed
+ * (csrc/dq_svd.hip), so every result is bit-identical from launch to launch and for every group size.
+ *   view_offsets [dev] [n_obj+1]    object o owns rows view_offsets[o] .. view_offsets[o+1]-1
+ *   P            [dev] [sumF][12]   row-major 3x4 projection K @ inv(T_wc)[:3,:] as float64
+ *   edges        [dev] [sumF][4]    bbox edge in pixels (float64), order x_min, x_max, y_min, y_max
+ *   mask         [dev] [sumF][4]    != 0: the edge is a constraint; 0: dropped (its edge value is not read)
+ *   max_views    largest view count of any object, 1 .. 16 * ODAM_SQ_MAX_VIEWS, else ODAM_E_LIMIT
+ *   out_Q        [dev] [n_obj][16]  row-major symmetric 4x4, normalised Q <- -Q / Q[3][3] (so Q[3][3] = -1)
+ *   out_eig      [dev] [n_obj][3]   eigenvalues of A: the smallest, the second smallest, the largest
+ *   status       [dev] [n_obj]      0 = an ellipsoid (the three eigenvalues of Q[:3,:3] + t t^T, t = -Q[:3,3], are > 0, the test of
+ *                DualQuadric.get_srt, sq_libs.py:257-280);  1 = not an ellipsoid, or Q[3][3] = 0 (then out_Q is the matrix of the
+ *                unit eigenvector, not normalised), or a Jacobi iteration reached its sweep limit (out_Q, out_eig from the last
+ *                iterate);  2 = fewer than 9 unmasked edges, or a view count outside 1 .. max_views: nothing computed, out_Q and
+ *                out_eig are NaN.  Other objects are unaffected.
+ */
+int odam_dq_svd_batch(odam_sq_ctx* ctx, int n_obj, const int* view_offsets, const double* P, const double* edges,
+                      const float* mask, int max_views, double* out_Q, double* out_eig, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,7 +121,7 @@ def _edge_lines(bbox, img_h, img_w, thr=EDGE_THRESHOLD):
     return out
 
 
-def _object_constraints(track, frame_to_img, img_h, img_w, thr=EDGE_THRESHOLD):
+def _object_constraints(track, frame_to_img, img_h, img_w, thr=EDGE_THRESHOLD, with_rows=False):
     """Per observed frame of one track, in image order, vectorised over the observations.
 
     tracking_gt_utils.py:145-211 walks every image, tests membership and builds per-frame dicts; here the
@@ -130,7 +130,8 @@ def _object_constraints(track, frame_to_img, img_h, img_w, thr=EDGE_THRESHOLD):
       tgt[n,4], mask[n,4] in the order x_min, x_max, y_min, y_max (sq_libs.py:438): mask = edge farther
       than `thr` px from the border (quadric_helper.py:87-107); tgt = float32(-float32(-pixel)), i.e. what
       `-gt` is after sq_libs.py:448 stores the line's last entry in a float32 tensor.
-    Returns class, image ids [n], tgt, mask, rotation matrices [n,3,3], t_wo [3], dims [n,3].
+    Returns class, image ids [n], tgt, mask, rotation matrices [n,3,3], t_wo [3], dims [n,3]; with_rows: and the track row of
+    every observation [n] (closed_form_quadrics reads the float64 edge values there).
     """
     frames = track[:, 0].astype(np.int32)
     if isinstance(frame_to_img, _UniqueFrames):
@@ -161,6 +162,8 @@ def _object_constraints(track, frame_to_img, img_h, img_w, thr=EDGE_THRESHOLD):
     lims = np.array([img_w, img_w, img_h, img_h], np.float64)
     mask = ((vals > thr) & (vals < lims - thr)).astype(np.float32)
     tgt = np.where(mask > 0, (-((-vals).astype(np.float32))), np.float32(0)).astype(np.float32)
+    if with_rows:
+        return obj_class, img_ids, tgt, mask, R, t_wo, sub[:, 6:9], rows
     return obj_class, img_ids, tgt, mask, R, t_wo, sub[:, 6:9]
 
 
@@ -284,6 +287,16 @@ def _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, 
     return out_dict
 
 
+def _frame_index(img_names):
+    """frame id -> image indices, in the form _object_constraints takes"""
+    if _UniqueFrames.applies(img_names):
+        return _UniqueFrames(img_names)
+    frame_to_img = {}
+    for i, fid in enumerate(img_names):
+        frame_to_img.setdefault(int(fid), []).append(i)  # every image whose id is in the track
+    return frame_to_img
+
+
 def _check_resume(resume, representation, n_objs):
     """the refusals of optim_process(resume=...), before any work: -> (state rows, track indices) or (None, None)"""
     if representation == "dual_quadric":
@@ -314,12 +327,7 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
     res_state = res_ids = None
     if resume is not None or return_state:
         res_state, res_ids = _check_resume(resume, representation, n_objs)
-    if _UniqueFrames.applies(img_names):
-        frame_to_img = _UniqueFrames(img_names)
-    else:
-        frame_to_img = {}
-        for i, fid in enumerate(img_names):
-            frame_to_img.setdefault(int(fid), []).append(i)  # every image whose id is in the track
+    frame_to_img = _frame_index(img_names)
     P_all = np.asarray(P_cws)
 
     inits, classes, bboxes_dl, fit_ids = [], [], [], []
@@ -400,3 +408,58 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
         out_dict["state"] = {"state": state_out if state_out is not None else np.zeros((0, _sq.STATE_FLOATS), np.float32),
                              "track_ids": np.asarray(fit_ids, np.int64), "representation": representation}
     return out_dict
+
+
+def _host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def closed_form_quadrics(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, n_views=3, fitter=None):
+    """The closed-form dual quadric of every track from its 2D box edges alone: the reference's compute_quadric_svd
+    (sq_libs.py:30-36) over load_pred_object's plane vectors (tracking_gt_utils.py:198-205), which its driver collects
+    (run_multi_view.py:25,36) and never uses.  No 3D guess enters -- translate, angle and dims of the detector only make
+    bboxes_dl -- and there is no iteration: all tracks with at least n_views valid views go to the GPU in ONE
+    SqFitter.quadric_svd call (float64; fixed accumulation order, so the result does not depend on the host's BLAS / LAPACK).
+
+    The rows are those of the fit (_object_constraints: same views, masks, first row of a frame), but the edge values are the
+    float64 pixels of the track columns [2, 4, 3, 5], not the fit's float32 targets, and P_cws is used in float64.
+    Returns {"quadrics", "bboxes_qc", "bboxes_dl", "status", "eig"}: bboxes_dl as optim_process; status [n] int32 and eig [n, 3]
+    (smallest, second smallest, largest eigenvalue of A; NaN where nothing was computed) as include/odam_sq.h gives them, with
+    status 2 also for a track that was not sent (fewer than n_views valid views).  Status 0: quadrics[i] is an sq.DualQuadric
+    (float64 Q, Q[3,3] = -1) and bboxes_qc[i] the oriented box of its compute_ellipsoid_points; otherwise quadrics[i] is None
+    and bboxes_qc[i] = bboxes_dl[i], the rule optim_process has for the tracks it does not fit."""
+    fitter = fitter or default_fitter()
+    n_objs = len(tracks)
+    frame_to_img = _frame_index(img_names)
+    P_all = np.asarray(P_cws, np.float64)
+    bboxes_dl, ids, counts, rows_P, rows_e, rows_m = [], [], [], [], [], []
+    for obj_id in range(n_objs):
+        track = np.asarray(tracks[obj_id])
+        _, img_ids, _, mask, R_wos, t_wo, dims, rows = _object_constraints(track, frame_to_img, img_h, img_w, with_rows=True)
+        T_wo = averaging_T_wos(R_wos, t_wo)
+        bboxes_dl.append(get_3d_box(np.mean(np.asarray(dims), axis=0), T_wo[:3, :3], T_wo[:3, 3]))
+        valid = mask.any(axis=1)       # frames with at least one constrained edge, as the fit counts them
+        if int(valid.sum()) >= n_views:
+            ids.append(obj_id)
+            counts.append(int(valid.sum()))
+            rows_P.append(P_all[img_ids[valid]].reshape(-1, 12))
+            rows_e.append(track[rows[valid]][:, [2, 4, 3, 5]].astype(np.float64))      # x_min, x_max, y_min, y_max
+            rows_m.append(mask[valid])
+    status = np.full(n_objs, 2, np.int32)
+    eig = np.full((n_objs, 3), np.nan)
+    quadrics = [None] * n_objs
+    bboxes_qc = list(bboxes_dl)
+    if ids:
+        out = fitter.quadric_svd(counts, np.concatenate(rows_P), np.concatenate(rows_e), np.concatenate(rows_m))
+        Q, st = _host(out["Q"]), np.asarray(out["status"], np.int32)
+        status[ids] = st
+        eig[ids] = _host(out["eig"])
+        good = [i for j, i in enumerate(ids) if st[j] == 0]
+        for j, i in enumerate(ids):
+            if st[j] == 0:
+                quadrics[i] = _sq.DualQuadric(Q[j].copy())
+        if good:      # oriented boxes of all ellipsoids in one native call (run_multi_view.py:66-67)
+            bl, _ = compute_oriented_bboxes(np.stack([quadrics[i].compute_ellipsoid_points(use_numpy=True)[0] for i in good]))
+            for i, b in zip(good, bl):
+                bboxes_qc[i] = b
+    return {"quadrics": quadrics, "bboxes_qc": bboxes_qc, "bboxes_dl": bboxes_dl, "status": status, "eig": eig}

@@ -666,6 +666,15 @@ class OdamProcess:
         self._refine_state = out.pop("state")
         return out
 
+    def closed_form_quadrics(self, n_views=3):
+        """The detector-independent shapes of the live tracks: multi_view.closed_form_quadrics (the closed-form dual quadric from
+        the 2D box edges, one launch, no iteration) on the views the tracks have now, from n_views valid views on.  Reads the tracks
+        and nothing else, like refine(), and keeps no state: association, refine() and optim_process go on as if it had never
+        been called.  Works for every representation."""
+        m = self.sequence_meta
+        return multi_view.closed_form_quadrics(self.tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
+                                               n_views=int(n_views), fitter=self._fitter())
+
     def optim_process(self, tracks, return_params=False):
         m = self.sequence_meta
         # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)

@@ -77,6 +77,17 @@ def _fit_resume_entry():
     return f
 
 
+# odam_dq_svd_batch as include/odam_sq.h declares it (tests/test_quadric_svd_host.py holds the two together)
+DQ_SVD_ARGTYPES = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 4
+
+
+def _dq_svd_entry():
+    f = _lib.lib().odam_dq_svd_batch
+    if f.argtypes is None:
+        f.argtypes, f.restype = DQ_SVD_ARGTYPES, ctypes.c_int
+    return f
+
+
 def cold_state(params0, representation):
     """[n, 32] float32 rows of fits that have not begun (include/odam_sq.h): what a track that starts cold gets inside a resumed call"""
     p = np.asarray(params0, np.float32).reshape(-1, 9)
@@ -330,6 +341,45 @@ class SqFitter:
     def set_dual_group_waves(self, waves):
         """objects per workgroup of fit_dual's launch (1, 2, 4, 8): scheduling only, results are bit-identical"""
         _lib.check(_lib.lib().odam_dq_set_group_waves(self._h, ctypes.c_int(int(waves))), "odam_dq_set_group_waves")
+
+    def quadric_svd(self, view_counts, P, edges, mask):
+        """Batched compute_quadric_svd (sq_libs.py:30-36) over the plane vectors of load_pred_object: the closed-form dual quadric
+        of every object from its 2D box edges, float64, ONE launch (include/odam_sq.h, odam_dq_svd_batch).
+
+        view_counts [n]; P [sumF,3,4]/[sumF,12] float64 projections; edges [sumF,4] float64 pixels in the order x_min, x_max,
+        y_min, y_max; mask [sumF,4] (0 = edge dropped).  numpy or torch, host or device.  Returns dict: Q [n,4,4] normalised
+        (Q[3,3] = -1) and eig [n,3] (smallest, second smallest, largest eigenvalue of A) as float64 device tensors, status [n]
+        int32 numpy: 0 an ellipsoid, 1 not one (or no normalisation / sweep limit), 2 nothing computed (fewer than 9 unmasked
+        edges or a view count outside 1..MAX_VIEWS; Q and eig NaN)."""
+        dev = self.device
+        n = len(view_counts)
+        vc = np.asarray(view_counts, np.int64).reshape(-1)
+        if n == 0:
+            return {"Q": torch.zeros(0, 4, 4, device=dev, dtype=torch.float64), "eig": torch.zeros(0, 3, device=dev, dtype=torch.float64),
+                    "status": np.zeros(0, np.int32)}
+        if vc.min() < 0:
+            raise _lib.OdamError(f"views per object must not be negative, got {vc.min()}")
+        as_dev = lambda x, dt: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=dev, dtype=dt).contiguous()
+        offs = np.zeros(n + 1, np.int64)
+        offs[1:] = np.cumsum(vc)
+        if offs[-1] >= 2 ** 31:
+            raise _lib.OdamError(f"{offs[-1]} views in one call: the offsets are 32-bit")
+        d_off = as_dev(offs.astype(np.int32), torch.int32)
+        d_P = as_dev(P, torch.float64).reshape(-1, 12)
+        d_e = as_dev(edges, torch.float64).reshape(-1, 4)
+        d_m = as_dev(mask, torch.float32).reshape(-1, 4)
+        assert d_P.shape[0] == offs[-1] and d_e.shape[0] == offs[-1] and d_m.shape[0] == offs[-1]
+        out_Q = torch.empty(n, 4, 4, device=dev, dtype=torch.float64)
+        out_eig = torch.empty(n, 3, device=dev, dtype=torch.float64)
+        status = torch.empty(n, device=dev, dtype=torch.int32)
+        # an object outside 1..MAX_VIEWS gets status 2 from the kernel; the launch limit itself must hold
+        max_views = int(min(max(int(vc.max()), 1), MAX_VIEWS))
+        with torch.cuda.device(dev), self._lock:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_dq_svd_entry()(self._h, n, _lib.ptr(d_off), _lib.ptr(d_P), _lib.ptr(d_e), _lib.ptr(d_m), max_views,
+                                       _lib.ptr(out_Q), _lib.ptr(out_eig), _lib.ptr(status), ctypes.c_void_p(stream)),
+                       "odam_dq_svd_batch")
+        return {"Q": out_Q, "eig": out_eig, "status": status.cpu().numpy()}
 
     def points(self, params):
         """compute_ellipsoid_points for [n,9] parameter rows -> [n,1000,3] device tensor."""
