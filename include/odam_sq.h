@@ -193,6 +193,55 @@ int odam_dq_set_group_waves(odam_sq_ctx* ctx, int waves);
 int odam_dq_svd_batch(odam_sq_ctx* ctx, int n_obj, const int* view_offsets, const double* P, const double* edges,
                       const float* mask, int max_views, double* out_Q, double* out_eig, int* status, void* stream);
 
+/*
+ * Reprojection: the 2D box a fitted object predicts in every one of its views, and how far that is from the detections.  The forward
+ * half of the reference's two box predictions, which it evaluates inside its fits only and never returns per view:
+ *   src/super_quadric/sq_libs.py:395-430   SuperQuadricOptimizer.constraint_2d   -> odam_sq_reproject_batch + odam_reproject_score_f32
+ *   src/super_quadric/sq_libs.py:289-314   DualQuadric.get_bbox                  -> odam_dq_reproject_batch + odam_reproject_score_f64
+ * ONE launch per call for all objects and all views (csrc/reproject.hip, arithmetic in csrc/reproject_core.h); stream-ordered, no
+ * synchronisation, no allocation.  view_offsets [dev][n_obj+1] as above; an object whose view count is outside 1 .. max_views owns
+ * no view.  max_views: 1 .. 16 * ODAM_SQ_MAX_VIEWS, else ODAM_E_LIMIT.  No call writes a word that no view or object owns.
+ *
+ * odam_sq_reproject_batch, float32 -- any of the three super-quadric representations, from surface points:
+ *   points       [dev] [n_obj][n_pts][3]  surface points (odam_sq_points_batch, or the fit's out_points); n_pts 1 .. 4096, else
+ *                ODAM_E_LIMIT
+ *   P            [dev] [sumF][12]   projections as float32, as the fit saw them
+ *   out_ext      [dev] [sumF][4]    x_min, x_max, y_min, y_max over the points with depth > 0.5, each u = q_x / (|q_z| + 1e-6); start
+ *                values +1e6 / -1e6, so a view without such a point holds exactly (1e6, -1e6, 1e6, -1e6); a NaN coordinate of such a
+ *                point makes that extent NaN (torch.min / torch.max); a zero is stored as +0
+ *   out_nvalid   [dev] [sumF]       points with depth > 0.5
+ * odam_dq_reproject_batch, float64 -- a dual quadric, fitted or closed-form:
+ *   Q            [dev] [n_obj][16]  row-major 4x4
+ *   P            [dev] [sumF][12]   projections as float64
+ *   out_ext      [dev] [sumF][4]    x_min, x_max, y_min, y_max of the conic C = (P Q) P^T
+ *   out_status   [dev] [sumF]       0; 1 = a discriminant 4 C_i2^2 - 4 C_ii C_22 is negative or NaN, or C_22 = 0: the four extents of
+ *                that view are NaN, every other view is unaffected
+ * odam_reproject_score_f32 / _f64 (T = float / double) -- per view and per object, from either of the above:
+ *   ext          [dev] [sumF][4]    predicted edges
+ *   bad          [dev] [sumF]       nullable; != 0: the view has no prediction (out_nvalid == 0, or out_status)
+ *   boxes        [dev] [sumF][4]    detected edges in pixels, x_min, x_max, y_min, y_max
+ *   mask         [dev] [sumF][4]    != 0: the edge is a constraint
+ *   img_w, img_h > 0, else ODAM_E_INVALID: the predicted box is clipped to the image for the IoU (detections are clipped already)
+ *   out_res      [dev] [sumF][4]    |ext - box| of a constrained edge, NaN -> 0; 0 of any other
+ *   out_iou      [dev] [sumF]       IoU of the detected box with the clipped predicted box; 0 for a bad view or an empty union
+ *   out_obj      [dev] [n_obj][4]   loss_2d = sum over the four directions of (sum of residuals / F), what the fits log;  mean_abs_px =
+ *                sum of residuals / n_edges (NaN without an edge);  mean_iou;  min_iou
+ *   out_obj_i    [dev] [n_obj][3]   worst_view (index inside the object of the first view with the smallest IoU), n_edges
+ *                (constrained edges), n_bad (bad views)
+ *   An object without views gets NaN x 4 and -1, 0, 0.  Sums run in the order of odam_dq_fit_batch (lane partials, XOR butterfly),
+ *   so every result is bit-identical from launch to launch and for every odam_dq_set_group_waves.
+ */
+int odam_sq_reproject_batch(odam_sq_ctx* ctx, int n_obj, const float* points, int n_pts, const int* view_offsets, const float* P,
+                            int max_views, float* out_ext, int* out_nvalid, void* stream);
+int odam_dq_reproject_batch(odam_sq_ctx* ctx, int n_obj, const double* Q, const int* view_offsets, const double* P, int max_views,
+                            double* out_ext, int* out_status, void* stream);
+int odam_reproject_score_f32(odam_sq_ctx* ctx, int n_obj, const int* view_offsets, const float* ext, const int* bad,
+                             const float* boxes, const float* mask, float img_w, float img_h, int max_views, float* out_res,
+                             float* out_iou, float* out_obj, int* out_obj_i, void* stream);
+int odam_reproject_score_f64(odam_sq_ctx* ctx, int n_obj, const int* view_offsets, const double* ext, const int* bad,
+                             const double* boxes, const float* mask, double img_w, double img_h, int max_views, double* out_res,
+                             double* out_iou, double* out_obj, int* out_obj_i, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -463,3 +463,91 @@ def closed_form_quadrics(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, n_vie
             for i, b in zip(good, bl):
                 bboxes_qc[i] = b
     return {"quadrics": quadrics, "bboxes_qc": bboxes_qc, "bboxes_dl": bboxes_dl, "status": status, "eig": eig}
+
+
+def reprojection(tracks, quadrics, img_names, T_wcs, P_cws, img_h, img_w, K, fitter=None):
+    """How well every fitted object explains the 2D detections of its track, view by view -- one yardstick for all five shapes.
+
+    quadrics[i] belongs to tracks[i] and is a SuperQuadric (any of "super_quadric", "cube", "quadric": scored from its surface
+    points through the forward half of constraint_2d, sq_libs.py:395-430, float32; an object without cached points gets them
+    from ONE fitter.points call on the parameter rows), an sq.DualQuadric (the iterative fit's float32 Q or the closed form's
+    float64 Q: scored through get_bbox, sq_libs.py:289-314, in float64), or None (skipped).  The rows are the fit's
+    (_object_constraints: first row of a frame, the 20 px mask rule, only views with at least one constrained edge); the
+    super-quadric group sees P_cws and the track columns [2, 4, 3, 5] as float32, as its fit did, the dual group as float64.
+    One reprojection launch and one score launch per group (SqFitter.reproject / reproject_dual / reprojection_score).
+
+    Returns a dict of numpy arrays.  Per object, length len(tracks): loss_2d (what the fits log), mean_abs_px, mean_iou, min_iou,
+    worst_img (image index of the first view with the smallest IoU), n_views, n_edges, n_bad (views without a prediction: no
+    surface point in front of the camera / a negative discriminant); an object that was skipped or has no valid view holds
+    NaN / -1 / 0.  Per view, flattened in track order: view_offsets [len(tracks) + 1], img_ids, pred [., 4] (x_min, x_max, y_min,
+    y_max), residual [., 4], iou."""
+    fitter = fitter or default_fitter()
+    n_objs = len(tracks)
+    if len(quadrics) != n_objs:
+        raise ValueError(f"{len(quadrics)} quadrics for {n_objs} tracks")
+    frame_to_img = _frame_index(img_names)
+    P_all = np.asarray(P_cws)
+    P_all64 = np.asarray(P_cws, np.float64)
+    counts = np.zeros(n_objs, np.int64)
+    img_of, group = {}, {"sq": [], "dq": []}
+    rows_P, rows_b, rows_m = {}, {}, {}
+    for i, q in enumerate(quadrics):
+        if q is None:
+            continue
+        if isinstance(q, SuperQuadric):
+            kind = "sq"
+        elif isinstance(q, _sq.DualQuadric):
+            kind = "dq"
+        else:
+            raise TypeError(f"quadrics[{i}] is a {type(q).__name__}: expected multi_view.SuperQuadric, sq.DualQuadric or None")
+        track = np.asarray(tracks[i])
+        _, img_ids, _, mask, _, _, _, rows = _object_constraints(track, frame_to_img, img_h, img_w, with_rows=True)
+        valid = mask.any(axis=1)       # frames with at least one constrained edge, as the fit counts them
+        if not valid.any():
+            continue
+        counts[i] = int(valid.sum())
+        img_of[i] = img_ids[valid]
+        group[kind].append(i)
+        edges = track[rows[valid]][:, [2, 4, 3, 5]]      # x_min, x_max, y_min, y_max
+        if kind == "sq":
+            rows_P[i] = P_all[img_ids[valid]].astype(np.float32).reshape(-1, 12)
+            rows_b[i] = edges.astype(np.float32)
+        else:
+            rows_P[i] = P_all64[img_ids[valid]].reshape(-1, 12)
+            rows_b[i] = edges.astype(np.float64)
+        rows_m[i] = mask[valid]
+    offs = np.zeros(n_objs + 1, np.int64)
+    offs[1:] = np.cumsum(counts)
+    total = int(offs[-1])
+    out = {"loss_2d": np.full(n_objs, np.nan), "mean_abs_px": np.full(n_objs, np.nan), "mean_iou": np.full(n_objs, np.nan),
+           "min_iou": np.full(n_objs, np.nan), "worst_img": np.full(n_objs, -1, np.int64), "n_views": counts,
+           "n_edges": np.zeros(n_objs, np.int64), "n_bad": np.zeros(n_objs, np.int64), "view_offsets": offs,
+           "img_ids": np.full(total, -1, np.int64), "pred": np.full((total, 4), np.nan), "residual": np.full((total, 4), np.nan),
+           "iou": np.full(total, np.nan)}
+    for kind, ids in group.items():
+        if not ids:
+            continue
+        vc = [int(counts[i]) for i in ids]
+        P, boxes, mask = (np.concatenate([r[i] for i in ids]) for r in (rows_P, rows_b, rows_m))
+        if kind == "sq":
+            pts = {i: quadrics[i]._points for i in ids if quadrics[i]._points is not None}
+            need = [i for i in ids if i not in pts]
+            if need:      # one call for all of them
+                got = _host(fitter.points(np.stack([quadrics[i].params for i in need])))
+                pts.update(zip(need, got))
+            r = fitter.reproject(np.stack([np.asarray(pts[i], np.float32) for i in ids]), vc, P)
+            bad = r["n_valid"] == 0
+        else:
+            r = fitter.reproject_dual(np.stack([np.asarray(quadrics[i].Q, np.float64) for i in ids]), vc, P)
+            bad = r["status"]
+        s = fitter.reprojection_score(r["ext"], bad, vc, boxes, mask, float(img_w), float(img_h))
+        dst = np.concatenate([np.arange(offs[i], offs[i + 1]) for i in ids])
+        out["img_ids"][dst] = np.concatenate([img_of[i] for i in ids])
+        out["pred"][dst] = _host(r["ext"])
+        out["residual"][dst] = _host(s["residual"])
+        out["iou"][dst] = _host(s["iou"])
+        for key in ("loss_2d", "mean_abs_px", "mean_iou", "min_iou", "n_edges", "n_bad"):
+            out[key][ids] = _host(s[key])
+        worst = _host(s["worst_view"]).astype(np.int64)
+        out["worst_img"][ids] = [out["img_ids"][offs[i] + w] if w >= 0 else -1 for i, w in zip(ids, worst)]
+    return out

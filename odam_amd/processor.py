@@ -675,6 +675,14 @@ class OdamProcess:
         return multi_view.closed_form_quadrics(self.tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                                n_views=int(n_views), fitter=self._fitter())
 
+    def reprojection(self, tracks, quadrics):
+        """How well quadrics[i] (a multi_view.SuperQuadric, an sq.DualQuadric or None) explains the detections of tracks[i], view by
+        view: multi_view.reprojection with this sequence's frames, poses and intrinsics -- the output of optim_process, refine() or
+        closed_form_quadrics scored on one scale.  Reads its arguments and the sequence and nothing else, and keeps no state."""
+        m = self.sequence_meta
+        return multi_view.reprojection(tracks, quadrics, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
+                                       fitter=self._fitter())
+
     def optim_process(self, tracks, return_params=False):
         m = self.sequence_meta
         # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)

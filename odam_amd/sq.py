@@ -88,6 +88,23 @@ def _dq_svd_entry():
     return f
 
 
+# the reprojection entry points as include/odam_sq.h declares them (tests/test_reproject_host.py holds the two together)
+_VP, _CI = ctypes.c_void_p, ctypes.c_int
+REPROJECT_ARGTYPES = {
+    "odam_sq_reproject_batch": [_VP, _CI, _VP, _CI, _VP, _VP, _CI, _VP, _VP, _VP],
+    "odam_dq_reproject_batch": [_VP, _CI, _VP, _VP, _VP, _CI, _VP, _VP, _VP],
+    "odam_reproject_score_f32": [_VP, _CI] + [_VP] * 5 + [ctypes.c_float] * 2 + [_CI] + [_VP] * 5,
+    "odam_reproject_score_f64": [_VP, _CI] + [_VP] * 5 + [ctypes.c_double] * 2 + [_CI] + [_VP] * 5,
+}
+
+
+def _reproject_entry(name):
+    f = getattr(_lib.lib(), name)
+    if f.argtypes is None:
+        f.argtypes, f.restype = REPROJECT_ARGTYPES[name], ctypes.c_int
+    return f
+
+
 def cold_state(params0, representation):
     """[n, 32] float32 rows of fits that have not begun (include/odam_sq.h): what a track that starts cold gets inside a resumed call"""
     p = np.asarray(params0, np.float32).reshape(-1, 9)
@@ -380,6 +397,103 @@ class SqFitter:
                                        _lib.ptr(out_Q), _lib.ptr(out_eig), _lib.ptr(status), ctypes.c_void_p(stream)),
                        "odam_dq_svd_batch")
         return {"Q": out_Q, "eig": out_eig, "status": status.cpu().numpy()}
+
+    def _view_rows(self, view_counts):
+        """view counts [n] (0 allowed: such an object owns no view) -> device offsets [n + 1] int32, rows in all, max_views of the launch"""
+        vc = np.asarray(view_counts, np.int64).reshape(-1)
+        if len(vc) and (vc.min() < 0 or vc.max() > MAX_VIEWS):
+            raise _lib.OdamError(f"views per object must be in 0..{MAX_VIEWS}, got {vc.min()}..{vc.max()}")
+        offs = np.zeros(len(vc) + 1, np.int64)
+        offs[1:] = np.cumsum(vc)
+        if offs[-1] >= 2 ** 31:
+            raise _lib.OdamError(f"{offs[-1]} views in one call: the offsets are 32-bit")
+        d_off = torch.from_numpy(offs.astype(np.int32)).to(self.device)
+        return d_off, int(offs[-1]), int(max(int(vc.max()) if len(vc) else 1, 1))
+
+    def _as_dev(self, x, dt):
+        return torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=self.device, dtype=dt).contiguous()
+
+    def reproject(self, points, view_counts, P):
+        """The 2D box of every object's surface points in every one of its views: the forward half of constraint_2d
+        (sq_libs.py:395-413), float32, ONE launch (include/odam_sq.h, odam_sq_reproject_batch).
+
+        points [n, n_pts, 3] (SqFitter.points, or a fit's "points"; n_pts 1..4096); view_counts [n]; P [sumF,3,4]/[sumF,12] as the
+        fit saw them.  numpy or torch, host or device.  Returns device tensors: ext [sumF,4] float32 (x_min, x_max, y_min, y_max;
+        (1e6, -1e6, 1e6, -1e6) where no point has depth > 0.5) and n_valid [sumF] int32."""
+        dev = self.device
+        d_pts = self._as_dev(points, torch.float32)
+        if d_pts.dim() != 3 or d_pts.shape[2] != 3:
+            raise ValueError(f"points must be [n, n_pts, 3], got {tuple(d_pts.shape)}")
+        d_off, rows, max_views = self._view_rows(view_counts)
+        n = d_off.shape[0] - 1
+        d_P = self._as_dev(P, torch.float32).reshape(-1, 12)
+        assert d_pts.shape[0] == n and d_P.shape[0] == rows
+        ext = torch.empty(rows, 4, device=dev, dtype=torch.float32)
+        nvalid = torch.empty(rows, device=dev, dtype=torch.int32)
+        if n and rows:      # (objects that own no view at all: nothing to write, and an empty tensor has no pointer to pass)
+            with torch.cuda.device(dev), self._lock:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_reproject_entry("odam_sq_reproject_batch")(
+                    self._h, n, _lib.ptr(d_pts), int(d_pts.shape[1]), _lib.ptr(d_off), _lib.ptr(d_P), max_views, _lib.ptr(ext),
+                    _lib.ptr(nvalid), ctypes.c_void_p(stream)), "odam_sq_reproject_batch")
+        return {"ext": ext, "n_valid": nvalid}
+
+    def reproject_dual(self, Q, view_counts, P):
+        """DualQuadric.get_bbox (sq_libs.py:289-314) of every object in every one of its views, float64, ONE launch
+        (odam_dq_reproject_batch).  Q [n,4,4] (float32 of the iterative fit or float64 of the closed form: computed in float64);
+        view_counts [n]; P [sumF,3,4]/[sumF,12] float64.  Returns device tensors: ext [sumF,4] float64 (x_min, x_max, y_min,
+        y_max) and status [sumF] int32 (1: negative discriminant or C_22 = 0, the view's extents are NaN)."""
+        dev = self.device
+        d_Q = self._as_dev(Q, torch.float64).reshape(-1, 16)
+        d_off, rows, max_views = self._view_rows(view_counts)
+        n = d_off.shape[0] - 1
+        d_P = self._as_dev(P, torch.float64).reshape(-1, 12)
+        assert d_Q.shape[0] == n and d_P.shape[0] == rows
+        ext = torch.empty(rows, 4, device=dev, dtype=torch.float64)
+        status = torch.empty(rows, device=dev, dtype=torch.int32)
+        if n and rows:
+            with torch.cuda.device(dev), self._lock:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_reproject_entry("odam_dq_reproject_batch")(
+                    self._h, n, _lib.ptr(d_Q), _lib.ptr(d_off), _lib.ptr(d_P), max_views, _lib.ptr(ext), _lib.ptr(status),
+                    ctypes.c_void_p(stream)), "odam_dq_reproject_batch")
+        return {"ext": ext, "status": status}
+
+    def reprojection_score(self, ext, bad, view_counts, boxes, mask, img_w, img_h):
+        """Predicted edges against detected boxes, per view and per object, ONE launch (odam_reproject_score_f32 / _f64: float64
+        when `ext` is float64, else float32).
+
+        ext [sumF,4] from reproject / reproject_dual; bad [sumF] or None (!= 0: a view without prediction -- n_valid == 0, or
+        status); view_counts [n]; boxes [sumF,4] detected edges in pixels (x_min, x_max, y_min, y_max); mask [sumF,4].  Returns
+        device tensors: residual [sumF,4], iou [sumF]; per object loss_2d, mean_abs_px, mean_iou, min_iou [n] and worst_view,
+        n_edges, n_bad [n] int32 (an object without views: NaN, -1, 0, 0)."""
+        dev = self.device
+        is64 = (ext.dtype == torch.float64) if torch.is_tensor(ext) else (np.asarray(ext).dtype == np.float64)
+        dt, name = (torch.float64, "odam_reproject_score_f64") if is64 else (torch.float32, "odam_reproject_score_f32")
+        d_ext = self._as_dev(ext, dt).reshape(-1, 4)
+        d_off, rows, max_views = self._view_rows(view_counts)
+        n = d_off.shape[0] - 1
+        d_bad = None if bad is None else self._as_dev(bad, torch.int32).reshape(-1)
+        d_box = self._as_dev(boxes, dt).reshape(-1, 4)
+        d_m = self._as_dev(mask, torch.float32).reshape(-1, 4)
+        assert d_ext.shape[0] == rows and d_box.shape[0] == rows and d_m.shape[0] == rows and (d_bad is None or d_bad.shape[0] == rows)
+        res = torch.empty(rows, 4, device=dev, dtype=dt)
+        iou = torch.empty(rows, device=dev, dtype=dt)
+        obj = torch.empty(n, 4, device=dev, dtype=dt)
+        obj_i = torch.empty(n, 3, device=dev, dtype=torch.int32)
+        if n and not rows:      # no object owns a view: the rows the kernel would write, without empty tensors' null pointers
+            obj.fill_(float("nan"))
+            obj_i.zero_()
+            obj_i[:, 0] = -1
+        elif n:
+            with torch.cuda.device(dev), self._lock:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_reproject_entry(name)(
+                    self._h, n, _lib.ptr(d_off), _lib.ptr(d_ext), _lib.ptr(d_bad), _lib.ptr(d_box), _lib.ptr(d_m), float(img_w),
+                    float(img_h), max_views, _lib.ptr(res), _lib.ptr(iou), _lib.ptr(obj), _lib.ptr(obj_i), ctypes.c_void_p(stream)),
+                    name)
+        return {"residual": res, "iou": iou, "loss_2d": obj[:, 0], "mean_abs_px": obj[:, 1], "mean_iou": obj[:, 2], "min_iou": obj[:, 3],
+                "worst_view": obj_i[:, 0], "n_edges": obj_i[:, 1], "n_bad": obj_i[:, 2]}
 
     def points(self, params):
         """compute_ellipsoid_points for [n,9] parameter rows -> [n,1000,3] device tensor."""
