@@ -86,12 +86,19 @@ def box3d_iou(c1, c2):
     return float(a[0]), float(b[0])
 
 
-def cost_matrix(tracks, bboxes_qc):
+def cost_matrix(tracks, bboxes_qc, fitter=None):
     """run_merge.py:92-118: 1 - 3D IoU for mergeable class pairs, 1 otherwise; symmetric, zero diagonal.
-    All mergeable pairs (i < j) go through one vectorised IoU evaluation."""
+    All mergeable pairs (i < j) go through one vectorised IoU evaluation -- on the host, or with an sq.SqFitter in ONE launch
+    over the n x n block (evaluate.box3d_iou_matrix, gate 2 = this class rule).  iou(b_i, b_j) and iou(b_j, b_i) need not be
+    equal (the clipper is not symmetric in winding), so the device path too reads the upper triangle i < j and mirrors it."""
     n = len(tracks)
     cls = np.array([int(np.median(t[:, 1])) for t in tracks])
     boxes = np.asarray([np.asarray(b, np.float64) for b in bboxes_qc]).reshape(n, 8, 3)
+    if fitter is not None:
+        from . import evaluate
+        iou = evaluate.box3d_iou_matrix(boxes, boxes, cls, cls, gate=2, fitter=fitter)["iou3d"].cpu().numpy()
+        cost = np.triu(1 - iou, 1)
+        return cost + cost.T
     sofa_chair = (cls == 4) | (cls == 5)             # run_merge.py:105-108
     ok = (cls[:, None] == cls[None, :]) | (sofa_chair[:, None] & sofa_chair[None, :])
     i, j = np.nonzero(np.triu(ok, 1))
@@ -123,14 +130,15 @@ def _merge_cluster(tracks, mask, img_names):
     return np.asarray(out)
 
 
-def merge_process(data, img_names):
-    """run_merge.py:79-130: data = optim_process output dict; returns the list of merged [n,82] tracks."""
+def merge_process(data, img_names, fitter=None):
+    """run_merge.py:79-130: data = optim_process output dict; returns the list of merged [n,82] tracks.  With a fitter the pair
+    costs come from the device (cost_matrix)."""
     tracks = data["tracks"]
     n = len(tracks)
     if n == 1:
         merged = tracks
     else:
-        cost = cost_matrix(tracks, data["bboxes_qc"])
+        cost = cost_matrix(tracks, data["bboxes_qc"], fitter)
         labels = AgglomerativeClustering(n_clusters=None, distance_threshold=0.95, metric="precomputed",
                                          linkage="average").fit(cost).labels_
         merged = [_merge_cluster(tracks, labels == c, img_names) for c in np.unique(labels)]

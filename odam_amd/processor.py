@@ -683,6 +683,13 @@ class OdamProcess:
         return multi_view.reprojection(tracks, quadrics, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                        fitter=self._fitter())
 
+    def evaluate(self, out, gt_boxes, gt_classes, threshold=0.25, min_views=1):
+        """A result dict of optim_process / refine against the ground truth of its scene (corners [k, 8, 3], class ids [k]):
+        evaluate.evaluate for the one scene -- the reference's eval_scan2cad.py matching and F1 table, two launches.  Reads its
+        arguments and nothing else, and keeps no state."""
+        from . import evaluate
+        return evaluate.evaluate([out], [(gt_boxes, gt_classes)], threshold, min_views, fitter=self._fitter())
+
     def optim_process(self, tracks, return_params=False):
         m = self.sequence_meta
         # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
