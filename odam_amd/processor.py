@@ -170,6 +170,8 @@ class OdamProcess:
         self._refine_state = None
         if getattr(self, "_win", None) is not None:
             self._win.reset()
+        if getattr(self.associator, "iou_tracker", False):
+            self._iou_tracker().reset()
 
     # ---- detection (processor.py:259-289) ----------------------------------------------------------
     def detect_frames(self, rgbs, frame_ids):
@@ -433,6 +435,10 @@ class OdamProcess:
     def process_frame(self, rgb, frame_id, T_wc, detections=None):
         """`detections`: optional rows for this frame computed earlier by `detect_frames` (here or on another
         rank); None -> run the detector now, as the reference does."""
+        if getattr(self.associator, "iou_tracker", False):
+            if detections is None:
+                detections = self.run_detector(rgb, frame_id, T_wc)
+            return self._track_frames_iou([frame_id], [T_wc], detections_list=[detections])
         if detections is not None and self._fast_ok():
             return self.process_frames([frame_id], [T_wc], [detections])
         return self._process_frame_host(rgb, frame_id, T_wc, detections)
@@ -493,7 +499,11 @@ class OdamProcess:
         idle while the other works.  Here a frame's device work is ONE native call (odam_assoc_step), everything the host can know
         before the assignment arrives -- the NEXT frame's camera quantities and track rows included -- is computed while the device works,
         and the track list is extended lazily (self.tracks folds the records in when it is read).  Only the Hungarian step and the
-        threshold tests stay between one frame's result and the next frame's launch."""
+        threshold tests stay between one frame's result and the next frame's launch.
+
+        With an odam_amd.tracker.IouTracker as the associator the frames take _track_frames_iou instead: one launch for all of them."""
+        if getattr(self.associator, "iou_tracker", False):
+            return self._track_frames_iou(frame_ids, T_wcs, detections_list=detections_list)
         n = len(frame_ids)
         if not self._fast_ok():
             for k in range(n):
@@ -634,6 +644,85 @@ class OdamProcess:
             self._pending_app = (ids, sel)
             self._n_tracks = n_tracks
             self._win_meta_stale = True
+
+    # ---- network-free association (odam_amd.tracker.IouTracker; the reference's src/scripts/run_tracking.py) ----------------------------
+    def _iou_tracker(self):
+        t = self.associator
+        if t.fitter is None and hasattr(self._fitter(), "_h") and torch.device(self._fitter().device) == torch.device(t.device):
+            t.fitter = self._fitter()      # one device context for the tracker and the fits
+        return t
+
+    def _track_frames_iou(self, frame_ids, T_wcs, detections_list=None, packed=None):
+        """The frames' association by the IoU tracker: ONE IouTracker.step call (one launch) for all of them, then the track rows on the
+        host -- _track_rows(..., with_code=False) of every frame, grouped by the returned ids into self.tracks, the same [n, 82] layout as
+        the network path builds, so optim_process, merge_process, refine, closed_form_quadrics, reprojection and evaluate work on them
+        unchanged.  usable_frames, T_wcs and P_cws get every frame, as always.
+
+        The rules are the reference TRACKER's (run_tracking.py), not the processor's: the first frame is not special (its detections start
+        tracks only where their score reaches the tracker's track_threshold, like any other frame's), and a detection below that threshold
+        that matches nothing is dropped.  This object's match_threshold / score_threshold belong to the network path and are not used.
+        The tracker's device state decides the matching; self.tracks is its host record and must not be edited between frames.
+        A frame that would exceed the tracker's max_tracks raises tracker.TrackOverflow: the frames before it are attached, that frame and
+        the later ones of the call are not (nor appended to usable_frames)."""
+        from . import parallel, tracker as _tracker
+        trk = self._iou_tracker()
+        m = self.sequence_meta
+        n = len(frame_ids)
+        if n == 0:
+            return None
+        if trk._state is None:
+            trk.reset()
+        if self._tracks is None or len(self._tracks) != trk.n_tracks[0]:
+            raise _tracker._lib.OdamError(f"the IoU tracker holds {trk.n_tracks[0]} tracks, self.tracks "
+                                          f"{None if self._tracks is None else len(self._tracks)}: init_sequence first, and do not edit the list between frames")
+        if packed is None:
+            blk, cnt = parallel.pack_detections([d if isinstance(d, np.ndarray) else np.asarray(d, np.float64).reshape(-1, 79)
+                                                 for d in detections_list])
+            step_in = (blk, cnt)
+        else:
+            step_in = packed
+        T_all = np.ascontiguousarray(np.stack([np.asarray(T, np.float64) for T in T_wcs]))
+        done, err = n, None
+        try:
+            ids = trk.step(step_in[0], step_in[1], np.asarray(frame_ids, np.int64), T_all, m.img_w, m.img_h)[0]
+        except _tracker.TrackOverflow as e:
+            ids, done, err = e.outputs[0], e.frame, e
+        ids = ids.cpu().numpy()
+        if packed is not None:
+            blk, cnt = packed[0].cpu().numpy(), packed[1].cpu().numpy()
+        for k in range(done):
+            self.usable_frames.append(frame_ids[k])
+            self.T_wcs.append(T_wcs[k])
+            self.P_cws.append(m.K @ np.linalg.inv(T_wcs[k])[:3, :])
+        tracks = self.tracks
+        add = {}
+        for k in range(done):
+            nk = int(min(max(int(cnt[k]), 0), parallel.MAX_DETS))
+            if nk == 0:
+                continue
+            self.run_associator = True
+            rows = self._track_rows(blk[k, :nk].astype(np.float64), np.asarray(T_wcs[k]), with_code=False)
+            for d in range(nk):
+                if ids[k, d] >= 0:
+                    add.setdefault(int(ids[k, d]), []).append(rows[d:d + 1])
+        for t in sorted(add):
+            if t < len(tracks):
+                tracks[t] = np.concatenate([tracks[t]] + add[t], axis=0)
+            else:
+                assert t == len(tracks), (t, len(tracks))
+                tracks.append(np.concatenate(add[t], axis=0))
+        self._n_tracks = len(tracks)
+        if err is not None:
+            raise err
+        return None
+
+    def track_frames_packed(self, blk, cnt, frame_ids, T_wcs):
+        """process_frames for an IouTracker on detect_frames_packed's device block (float32 [N, 30, 15] + int32 [N]): the block goes into
+        the tracker's launch as it is -- the detections do not visit the host before the tracks are built; they are read back once,
+        afterwards, for the host's track rows.  Same tracks as process_frames on the unpacked rows."""
+        if not getattr(self.associator, "iou_tracker", False):
+            raise TypeError("track_frames_packed needs an odam_amd.tracker.IouTracker as the associator")
+        return self._track_frames_iou(frame_ids, T_wcs, packed=(blk, cnt))
 
     # ---- back end (processor.py:347-368) -----------------------------------------------------------
     def merge_process(self, data):
