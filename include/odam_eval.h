@@ -56,6 +56,63 @@ int odam_box3d_match_batch(odam_sq_ctx* ctx, int n_scene, const int* a_off, cons
                            const double* iou3d, const int* cls_pred, const int* cls_gt, double threshold, int n_class, int max_gt,
                            int* out_counts, int* out_claimed, int* out_gt_match, void* stream);
 
+/*
+ * odam_det_ap -- average precision of score-ranked predictions, every class and every image in one call: the reference's
+ * src/utils/eval_utils.py voc_ap (:43-74) and eval_det_cls (:86-176) for all classes at once (csrc/det_ap.hip, arithmetic in
+ * csrc/det_ap_core.h, restated by tests/det_ap_ref.py).  An image is a scene or a frame.  SIX launches per call, whatever the
+ * sizes (overlap, count, rank, claim, flag, curve); stream-ordered, no synchronisation, no allocation, binary64.
+ *
+ *   kind         how a pair's overlap is found
+ *                0  axis-aligned boxes of 8 corners, as eval_det_cls:147-152 computes it (min / max per axis, box_utils.iou_3d)
+ *                1  read from `iou`, as odam_box3d_iou_batch wrote it with gate = 1: predictions are rows (A), ground truth columns
+ *                   (B), pred_off / gt_off / pair_off / n_pairs are that call's a_off / b_off / pair_off / n_pairs
+ *                2  detection rows [n_image][30][15] float32 as odam_detr_select_pack writes them, 3D: the box t_co -+ dims / 2
+ *                   (columns 9-11, 6-8; DETR.nms_3d's box) in binary64, then iou_3d
+ *                3  detection rows, 2D: columns 2-5 with box_utils.iou_2d
+ *   n_image, n_pred, n_gt, n_class   the sizes every launch is shaped by (host copies).  n_class 1 .. 64.  n_pred counts SLOTS:
+ *                for kinds 2, 3 n_pred == n_gt == 30 n_image (ODAM_AP_ROW_SLOTS), else ODAM_E_INVALID.  n_pred above
+ *                ODAM_AP_MAX_PRED is ODAM_E_LIMIT, before any launch: the ranking counts pairs of predictions
+ *   pred_off, gt_off  [dev] int32.  Kinds 0, 1: [n_image+1] offsets, image i owns the rows off[i] .. off[i+1]-1.  Kinds 2, 3:
+ *                [n_image] counts, frame f owns the slots 30 f .. 30 f + count[f] - 1; a slot past the count is owned by nobody,
+ *                is never read and gets no output word
+ *   pred_box, gt_box  [dev] kind 0: float64 [n][8][3]; kinds 2, 3: the float32 blocks (class = column 1, score = column 14; a class
+ *                word that is not in [0, 64) is no class); kind 1: not read, may be null
+ *   cls_pred, cls_gt [dev] int32 [n_pred], [n_gt], score [dev] float64 [n_pred]: kinds 0, 1; not read for kinds 2, 3
+ *   pair_off [dev] int64 [n_image+1], iou [dev] float64 [n_pairs], n_pairs: kind 1 only
+ *   scratch      [dev] int32 [2 n_pred + 2 n_gt]; every word of it may be written, none past it
+ *
+ * Per prediction d (out_* [dev] [n_pred]):
+ *   out_ovmax    float64: the largest IoU with a ground-truth box of ITS image and ITS class, boxes in their given order, replaced
+ *                when `iou > ovmax` from -inf: the first of equal maxima wins, a NaN never; -inf when there is no such box
+ *   out_jmax     int32: that box's index among ALL ground truth of the image (classes mixed, as given), -1 when none
+ *   out_rank     int32: position inside its class by descending score; equal scores keep their input order and a NaN score ranks
+ *                after every number (np.argsort(-confidence) leaves the order of equal keys open: this is a deviation)
+ *   out_is_tp    int32: 1 when ovmax > ovthresh and no prediction of the class ranked before it has the same image, the same
+ *                jmax and ovmax > ovthresh; else 0
+ * Per ground-truth box (out_gt_claim [dev] [n_gt] int32): the index d of the true positive on it, else -1.
+ * Per class c (out_npos, out_npred, out_ap [dev] [n_class]; out_cls_off [dev] [n_class+1] int32, cls_off[c+1] - cls_off[c] = npred[c]):
+ *   out_order    [dev] int32, words cls_off[c] + r: the prediction of rank r
+ *   out_tp, out_fp   [dev] int32, out_rec, out_prec [dev] float64, same words: inclusive prefix sums in rank order,
+ *                rec = tp / npos, prec = tp / max(tp + fp, eps).  These five are [n_pred] long; words from cls_off[n_class] on are
+ *                not written
+ *   out_ap       voc_ap: the 11-point form when use_07_metric != 0, else the area under the precision envelope, summed in the
+ *                order tests/det_ap_ref.py::ap_area restates.  npos == 0: NaN in both forms (the reference's 11-point form would
+ *                give 0), with rec NaN and prec as computed; leave such a class out of a mean.  npos > 0, npred == 0: 0.
+ * A prediction or box counts under NO class when its class id is outside 0 .. n_class-1, or (offsets that contradict the sizes
+ * are not trusted) when no image's range off[i] <= d < off[i+1], inside [0, n], holds it, or, for a prediction, when its image's
+ * ground-truth range or pair block does not lie inside [0, n_gt] / [0, n_pairs].  It is counted nowhere, matches nothing and has
+ * no rank: out_ovmax NaN, out_jmax -1, out_rank -1, out_is_tp -1; out_gt_claim -1.  A frame count outside 0 .. 30 owns no slot.
+ * n_pred == 0 (and n_image == 0) is ODAM_OK: the per-class words are still written.
+ */
+#define ODAM_AP_MAX_PRED 32768
+#define ODAM_AP_ROW_SLOTS 30
+int odam_det_ap(odam_sq_ctx* ctx, int kind, int n_image, int n_pred, int n_gt, int n_class, const int* pred_off, const int* gt_off,
+                const void* pred_box, const void* gt_box, const int* cls_pred, const int* cls_gt, const double* score,
+                const long long* pair_off, const double* iou, long long n_pairs, double ovthresh, int use_07_metric, int* scratch,
+                double* out_ovmax, int* out_jmax, int* out_rank, int* out_is_tp, int* out_gt_claim, int* out_order, int* out_npos,
+                int* out_npred, int* out_cls_off, double* out_ap, int* out_tp, int* out_fp, double* out_rec, double* out_prec,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,8 @@ _VP, _CI, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 EVAL_ARGTYPES = {
     "odam_box3d_iou_batch": [_VP, _CI, _VP, _VP, _VP, _LL, _VP, _VP, _VP, _VP, _CI, _VP, _VP, _VP],
     "odam_box3d_match_batch": [_VP, _CI, _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, _CI, _CI, _VP, _VP, _VP, _VP],
+    "odam_det_ap": [_VP, _CI, _CI, _CI, _CI, _CI, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _LL, ctypes.c_double, _CI, _VP,
+                    _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
 
 
@@ -228,4 +230,178 @@ def compare_maps(out_a, out_b, threshold=0.25, min_views=1, fitter=None):
     out["matched"] = np.stack([ids_a[gm[hit]], gt[2][hit]], axis=1) if len(hit) else np.zeros((0, 2), np.int64)
     out["matched_iou"] = iou[gm[hit], hit] if len(hit) else np.zeros(0)
     out["gt_ids"] = gt[2]
+    return out
+
+
+# ---- average precision: the reference's src/utils/eval_utils.py eval_det / eval_det_cls / voc_ap ------------------------------------
+# Score-ranked precision / recall curves and AP per class, every class and every image (scene or frame) in one call of six launches
+# (odam_det_ap: include/odam_eval.h, csrc/det_ap.hip).  Where this departs from the reference, and why, is in DESIGN 6k:
+#   - equal scores keep their input order and a NaN score ranks last (np.argsort leaves ties open);
+#   - a class with ground truth and no prediction has AP 0 and empty curves (the reference raises KeyError);
+#   - a class with predictions and no ground truth has AP NaN in both forms and is left out of the mean;
+#   - a class id outside 0 .. n_class-1 is counted nowhere; its per-prediction words are NaN / -1.
+MAX_AP_PRED = 32768    # prediction slots per call (ODAM_AP_MAX_PRED: the ranking counts pairs)
+ROW_SLOTS = 30         # detection rows per frame of a packed block (ODAM_AP_ROW_SLOTS)
+_AP_KINDS = {"aabb": 0, "obb": 1, "aabb3d": 2, "box2d": 3}
+_AP_OUT = (("ovmax", "p", torch.float64), ("jmax", "p", torch.int32), ("rank", "p", torch.int32), ("is_tp", "p", torch.int32),
+           ("gt_claim", "g", torch.int32), ("order", "p", torch.int32), ("npos", "c", torch.int32), ("npred", "c", torch.int32),
+           ("cls_off", "c1", torch.int32), ("ap", "c", torch.float64), ("tp", "p", torch.int32), ("fp", "p", torch.int32),
+           ("rec", "p", torch.float64), ("prec", "p", torch.float64))
+
+
+def _ap_launch(kind, n_image, n_pred, n_gt, n_class, d_poff, d_goff, pred_box, gt_box, cls_p, cls_g, score, d_pair_off, iou, n_pairs,
+               ovthresh, use_07_metric, fitter, dev):
+    """odam_det_ap on device inputs -> its fourteen outputs as device tensors (the ragged ones are [n_pred] long; class c owns the
+    words cls_off[c] .. cls_off[c+1]-1, the rest is not written)"""
+    if n_pred > MAX_AP_PRED:      # before any launch; the entry point answers the same (ODAM_E_LIMIT)
+        raise _lib.OdamError(f"average precision: {n_pred} prediction slots in one call, more than {MAX_AP_PRED} (ODAM_E_LIMIT)")
+    size = {"p": max(n_pred, 1), "g": max(n_gt, 1), "c": n_class, "c1": n_class + 1}
+    out = {name: torch.empty(size[s], device=dev, dtype=dt) for name, s, dt in _AP_OUT}
+    scratch = torch.empty(max(2 * n_pred + 2 * n_gt, 1), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_entry("odam_det_ap")(
+            fitter._h, int(kind), int(n_image), int(n_pred), int(n_gt), int(n_class), _lib.ptr(d_poff), _lib.ptr(d_goff),
+            _lib.ptr(pred_box), _lib.ptr(gt_box), _lib.ptr(cls_p), _lib.ptr(cls_g), _lib.ptr(score), _lib.ptr(d_pair_off),
+            _lib.ptr(iou), int(n_pairs), float(ovthresh), int(bool(use_07_metric)), _lib.ptr(scratch),
+            *[_lib.ptr(out[name]) for name, _, _ in _AP_OUT], ctypes.c_void_p(stream)), "odam_det_ap")
+    keep = {"p": n_pred, "g": n_gt, "c": n_class, "c1": n_class + 1}
+    return {name: out[name][:keep[s]] for name, s, _ in _AP_OUT}
+
+
+def average_precision(preds, gts, ovthresh=0.25, use_07_metric=False, iou="aabb", fitter=None, n_class=N_CLASS):
+    """eval_det_cls (eval_utils.py:86-176) for every class over many images at once.  preds: list, one entry per image, of
+    (boxes [k, 8, 3], classes [k], scores [k]); gts: list of (boxes [k, 8, 3], classes [k]).  iou = "aabb": the axis-aligned boxes
+    of the corners, which is what the reference computes whatever get_iou_func says; "obb": the oriented-box IoU its default
+    argument names (odam_box3d_iou_batch, gate 1, one more launch).
+
+    Returns device tensors -- per prediction "ovmax", "jmax" (index among all ground truth of its image), "rank" (inside its class),
+    "is_tp"; per ground-truth box "gt_claim" (the true positive on it, an index into the concatenated predictions, or -1); per class
+    "npos", "npred", "ap", "cls_off" and, in rank order from cls_off[c], "order", "tp", "fp", "rec", "prec" -- and the host offsets
+    "pred_off", "gt_off"."""
+    fitter = _default_fitter(fitter)
+    dev = fitter.device
+    if len(preds) != len(gts):
+        raise ValueError("one entry per image in both lists")
+    if iou not in ("aabb", "obb"):
+        raise ValueError(f'iou must be "aabb" or "obb", got {iou!r}')
+    pad = lambda t, dt: t if t.shape[0] else torch.zeros(1, device=dev, dtype=dt)
+    sc = _cat([torch.as_tensor(np.asarray(p[2]) if not torch.is_tensor(p[2]) else p[2]).to(device=dev, dtype=torch.float64).reshape(-1)
+               for p in preds], (0,), torch.float64, dev)
+    if iou == "obb":
+        r = _iou_launch([p[0] for p in preds], [g[0] for g in gts], [p[1] for p in preds], [g[1] for g in gts], 1, fitter, False)
+        d_poff, d_goff, d_pair, d_cp, d_cg, iou_buf = r["_dev"]
+        po, go, n_pairs, A, B = r["a_off"], r["b_off"], int(r["pair_off"][-1]), None, None
+    else:
+        A = [_boxes(p[0], dev) for p in preds]; B = [_boxes(g[0], dev) for g in gts]
+        po = _offsets([len(x) for x in A]); go = _offsets([len(x) for x in B])
+        d_cp = _cat([_classes(p[1], dev) for p in preds], (0,), torch.int32, dev)
+        d_cg = _cat([_classes(g[1], dev) for g in gts], (0,), torch.int32, dev)
+        A = pad(_cat(A, (0, 8, 3), torch.float64, dev), torch.float64); B = pad(_cat(B, (0, 8, 3), torch.float64, dev), torch.float64)
+        d_poff = torch.from_numpy(po.astype(np.int32)).to(dev); d_goff = torch.from_numpy(go.astype(np.int32)).to(dev)
+        d_pair = iou_buf = None
+        n_pairs = 0
+    n_pred, n_gt = int(po[-1]), int(go[-1])
+    if d_cp.shape[0] != n_pred or d_cg.shape[0] != n_gt or sc.shape[0] != n_pred:
+        raise ValueError("one class per box and one score per prediction")
+    out = _ap_launch(_AP_KINDS[iou], len(preds), n_pred, n_gt, n_class, d_poff, d_goff, A, B, pad(d_cp, torch.int32),
+                     pad(d_cg, torch.int32), pad(sc, torch.float64), d_pair, iou_buf, n_pairs, ovthresh, use_07_metric, fitter, dev)
+    out.update(pred_off=po, gt_off=go)
+    return out
+
+
+def ap_table(r):
+    """The host summary of average_precision's / detections_ap's device tensors: {"ap": [n_class] (NaN where the class has no ground
+    truth), "mAP": the mean over the classes with ground truth (NaN when there is none), "npos", "npred"}."""
+    ap = r["ap"].cpu().numpy(); npos = r["npos"].cpu().numpy(); npred = r["npred"].cpu().numpy()
+    have = npos > 0
+    return {"ap": ap, "mAP": float(ap[have].mean()) if have.any() else float("nan"), "npos": npos, "npred": npred}
+
+
+def eval_det(pred_all, gt_all, ovthresh=0.25, use_07_metric=False, iou="aabb", fitter=None):
+    """The reference's eval_det (eval_utils.py:185-235) without its prints and plots: pred_all {img_id: [(class, box [8, 3], score)]},
+    gt_all {img_id: [(class, box [8, 3])]} -> (rec, prec, ap), dicts keyed by class, rec / prec numpy arrays in rank order.  Classes
+    are any hashable names (at most 64).  A class with ground truth and no prediction has AP 0 and empty curves (the reference
+    raises KeyError); one with predictions and no ground truth has AP NaN."""
+    names, imgs = [], list(pred_all.keys()) + [k for k in gt_all.keys() if k not in pred_all]
+    for src in (pred_all, gt_all):      # the order in which the reference's `gt` dict meets the classes (:200-217)
+        for img in src.keys():
+            for item in src[img]:
+                if item[0] not in names:
+                    names.append(item[0])
+    if len(names) > 64:
+        raise ValueError(f"{len(names)} classes, more than 64")
+    if not names:
+        return {}, {}, {}
+    cid = {n: i for i, n in enumerate(names)}
+    preds = [(np.asarray([b for _, b, _ in pred_all.get(i, [])], np.float64).reshape(-1, 8, 3),
+              np.asarray([cid[c] for c, _, _ in pred_all.get(i, [])], np.int32),
+              np.asarray([s for _, _, s in pred_all.get(i, [])], np.float64)) for i in imgs]
+    gts = [(np.asarray([b for _, b in gt_all.get(i, [])], np.float64).reshape(-1, 8, 3),
+            np.asarray([cid[c] for c, _ in gt_all.get(i, [])], np.int32)) for i in imgs]
+    r = average_precision(preds, gts, ovthresh, use_07_metric, iou, fitter, n_class=len(names))
+    off = r["cls_off"].cpu().numpy(); rec = r["rec"].cpu().numpy(); prec = r["prec"].cpu().numpy(); ap = r["ap"].cpu().numpy()
+    return ({n: rec[off[i]:off[i + 1]] for i, n in enumerate(names)}, {n: prec[off[i]:off[i + 1]] for i, n in enumerate(names)},
+            {n: float(ap[i]) for i, n in enumerate(names)})
+
+
+def prediction_scores(out, min_views=1):
+    """A confidence for every object predictions_from_result keeps, in its order: the mean of the scores of the object's detections
+    (track column 13).  The reference defines no score for a fitted object; this definition is the project's own."""
+    boxes, classes, ids = predictions_from_result(out, min_views)
+    return np.asarray([float(np.mean(np.asarray(out["tracks"][i], np.float64)[:, 13])) for i in ids], np.float64)
+
+
+def evaluate_ap(results, gts, ovthresh=0.25, use_07_metric=False, iou="aabb", min_views=1, fitter=None):
+    """average_precision over many scenes: results = list of result dicts (optim_process's output), scored by prediction_scores;
+    gts = list of (boxes [k, 8, 3], classes [k]).  Returns ap_table's dict plus, per scene, "is_tp", "ovmax", "gt_claim" (index inside
+    the scene's kept predictions, or -1) and "pred_ids", and per class "rec" / "prec" (lists of numpy arrays in rank order)."""
+    preds = [predictions_from_result(r, min_views)[:2] + (prediction_scores(r, min_views),) for r in results]
+    ids = [predictions_from_result(r, min_views)[2] for r in results]
+    r = average_precision(preds, [g[:2] for g in gts], ovthresh, use_07_metric, iou, fitter)
+    out = ap_table(r)
+    po, go = r["pred_off"], r["gt_off"]
+    is_tp, ovmax, claim = r["is_tp"].cpu().numpy(), r["ovmax"].cpu().numpy(), r["gt_claim"].cpu().numpy()
+    off, rec, prec = r["cls_off"].cpu().numpy(), r["rec"].cpu().numpy(), r["prec"].cpu().numpy()
+    n = len(preds)
+    out.update(ovthresh=ovthresh, pred_ids=ids, is_tp=[is_tp[po[s]:po[s + 1]] for s in range(n)],
+               ovmax=[ovmax[po[s]:po[s + 1]] for s in range(n)],
+               gt_claim=[np.where(claim[go[s]:go[s + 1]] >= 0, claim[go[s]:go[s + 1]] - po[s], -1) for s in range(n)],
+               rec=[rec[off[c]:off[c + 1]] for c in range(N_CLASS)], prec=[prec[off[c]:off[c + 1]] for c in range(N_CLASS)])
+    return out
+
+
+def compare_maps_ap(out_a, out_b, ovthresh=0.25, use_07_metric=False, iou="aabb", min_views=1, fitter=None):
+    """Map A, ranked by prediction_scores, against map B as the ground truth (two result dicts of the same scene): evaluate_ap's dict
+    for the one scene, plus "gt_ids", the object ids of B that were kept."""
+    gt = predictions_from_result(out_b, min_views)
+    out = evaluate_ap([out_a], [gt[:2]], ovthresh, use_07_metric, iou, min_views, fitter)
+    out["gt_ids"] = gt[2]
+    return out
+
+
+def detections_ap(blk_pred, cnt_pred, blk_gt, cnt_gt, iou="aabb3d", ovthresh=0.25, use_07_metric=False, fitter=None, n_class=N_CLASS):
+    """One detector run against another, frame by frame, without the detections leaving the device: two blocks of equal frame count
+    as OdamProcess.detect_frames_packed returns them (float32 [F, 30, 15] and int32 [F] on the device), the second taken as the
+    ground truth.  Images are frames; class = column 1, score = column 14; iou = "aabb3d": the box t_co -+ dims / 2 of DETR.nms_3d
+    (columns 9-11, 6-8); "box2d": the image box (columns 2-5).  Slots past a frame's count are ignored, whatever they hold.
+    Returns ap_table's dict (the only copy to the host) plus "device": the call's outputs as device tensors over the F * 30 slots."""
+    fitter = _default_fitter(fitter)
+    if iou not in ("aabb3d", "box2d"):
+        raise ValueError(f'iou must be "aabb3d" or "box2d", got {iou!r}')
+    for b, c in ((blk_pred, cnt_pred), (blk_gt, cnt_gt)):
+        if not (torch.is_tensor(b) and b.is_cuda and b.dtype == torch.float32 and b.dim() == 3 and tuple(b.shape[1:]) == (ROW_SLOTS, 15)
+                and b.is_contiguous() and torch.is_tensor(c) and c.is_cuda and c.dtype == torch.int32 and c.is_contiguous()
+                and tuple(c.shape) == (b.shape[0],)):
+            raise ValueError("detections_ap: contiguous device tensors float32 [F, 30, 15] and int32 [F]")
+    if blk_pred.shape[0] != blk_gt.shape[0]:
+        raise ValueError("detections_ap: two blocks of equal frame count")
+    F = int(blk_pred.shape[0])
+    dev = blk_pred.device
+    one = torch.zeros(1, device=dev, dtype=torch.int32)
+    one_f = torch.zeros(ROW_SLOTS * 15, device=dev, dtype=torch.float32)
+    r = _ap_launch(_AP_KINDS[iou], F, F * ROW_SLOTS, F * ROW_SLOTS, n_class, cnt_pred if F else one, cnt_gt if F else one,
+                   blk_pred if F else one_f, blk_gt if F else one_f, None, None, None, None, None, 0, ovthresh, use_07_metric, fitter, dev)
+    out = ap_table(r)
+    out["device"] = r
     return out

@@ -779,6 +779,20 @@ class OdamProcess:
         from . import evaluate
         return evaluate.evaluate([out], [(gt_boxes, gt_classes)], threshold, min_views, fitter=self._fitter())
 
+    def evaluate_ap(self, out, gt_boxes, gt_classes, ovthresh=0.25, use_07_metric=False, iou="aabb", min_views=1):
+        """A result dict of optim_process / refine against the ground truth of its scene, score-ranked: evaluate.evaluate_ap for the
+        one scene -- the reference's eval_det_cls / voc_ap curves and average precision per class, objects ranked by the mean score
+        of their detections.  Reads its arguments and nothing else, and keeps no state."""
+        from . import evaluate
+        return evaluate.evaluate_ap([out], [(gt_boxes, gt_classes)], ovthresh, use_07_metric, iou, min_views, fitter=self._fitter())
+
+    def detections_ap(self, blk, cnt, other_blk, other_cnt, iou="aabb3d", ovthresh=0.25, use_07_metric=False):
+        """The detections of one run (detect_frames_packed's block and counts) against those of another run of the same frames as
+        the ground truth, frame by frame, on the device: evaluate.detections_ap -- what a narrower number type costs at the level of
+        detections, before association and fitting.  Reads its arguments and nothing else, and keeps no state."""
+        from . import evaluate
+        return evaluate.detections_ap(blk, cnt, other_blk, other_cnt, iou, ovthresh, use_07_metric, fitter=self._fitter())
+
     def optim_process(self, tracks, return_params=False):
         m = self.sequence_meta
         # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
