@@ -242,6 +242,67 @@ int odam_reproject_score_f64(odam_sq_ctx* ctx, int n_obj, const int* view_offset
                              const double* boxes, const float* mask, double img_w, double img_h, int max_views, double* out_res,
                              double* out_iou, double* out_obj, int* out_obj_i, void* stream);
 
+/*
+ * The prelude of a fit pass on the device: what run_multi_view.py:44-62 does per track before it fits -- the views, constraint rows
+ * and initial shape of EVERY track in one launch (csrc/sq_prepare.hip), one workgroup per track, no device-wide barrier.  Replaces, for
+ * sequences whose frame ids are all different:
+ *   src/utils/tracking_gt_utils.py:145-211, 59-66   load_pred_object (views of a track in image order, first row of a frame id wins;
+ *                                                   class = median; t_wo = mean) and averaging_T_wos
+ *   src/super_quadric/quadric_helper.py:69-109      bbox_to_lines (an edge is a constraint when it is farther than thr from the border)
+ *   src/scripts/run_multi_view.py:44-62             the views with at least one constrained edge, get_3d_box of the detector's pose
+ *   src/super_quadric/sq_libs.py:353-371, 41-58     SuperQuadricOptimizer.__init__ / QuadricOptimizer.__init__ (the initial parameters)
+ * Every rotation averaged is a rotz(a), quaternion (0, 0, sin a/2, cos a/2), so the mean rotation of averaging_T_wos (the leading
+ * eigenvector of sum q q^T) is rotz(yaw) with yaw = atan2(sum sin a, sum cos a): no eigen-solver.
+ * Stream-ordered, no synchronisation, no allocation.
+ *   row_off      [dev] [n_obj+1]    track o owns rows row_off[o] .. row_off[o+1]-1
+ *   rows         [dev] [R][14]      float64: the first 14 columns of every track row (frame id, class, x_min, y_min, x_max, y_max,
+ *                                   dims[3], t_wo[3], yaw, one more), track after track
+ *   max_rows     largest row count of any track as the caller knows it on the host: sizes the workgroup and its LDS (8 bytes per row of
+ *                the next power of two).  A value above ODAM_SQ_PREPARE_MAX_ROWS is taken as that.  A track with more rows than the
+ *                launch was sized for gets status 3, whatever else is true of it; < 1 is ODAM_E_INVALID.
+ *   img_ids      [dev] [n_img]      int64 frame ids of the images, ascending, all different, |id| < 2^31
+ *   img_order    [dev] [n_img]      image index of img_ids[i] (an entry outside 0 .. n_img-1 is an image no row can be a view of)
+ *   P_cws        [dev] [n_img][12]  float64 projection of every image
+ *   img_w, img_h, thr               edge e of a view is a constraint when thr < value < lim - thr (both strict, float64),
+ *                                   lim = img_w, img_w, img_h, img_h for the order x_min, x_max, y_min, y_max (columns 2, 4, 3, 5)
+ *   representation                  ODAM_SQ_SUPER_QUADRIC / _CUBE / _QUADRIC, or ODAM_SQ_DUAL_QUADRIC
+ * Per track (o):
+ *   cls          [dev] [n_obj]      int(median of column 1 over ALL rows), an even count averaging the two middle values; -1 when a class
+ *                                   value is not an integer in 0..63 (or the track has no row)
+ *   n_obs        [dev] [n_obj]      views: rows whose frame id (column 0 truncated to int32; a value outside int32 is no id) is in
+ *                                   img_ids, the lowest row of each id, in ascending image index
+ *   n_valid      [dev] [n_obj]      views with at least one constrained edge
+ *   init         [dev] [n_obj][9]   float32 of (translation[3], yaw, sqrt(scales / 2)[3], shapes[2] = -0.0 or, for the cube, -10000);
+ *                                   for ODAM_SQ_DUAL_QUADRIC [n_obj][5] = (translation[3], yaw, 1)
+ *   half_dims    [dev] [n_obj][3]   ODAM_SQ_DUAL_QUADRIC only (else nullable, not written): float32(scales / 2)
+ *   pose         [dev] [n_obj][7]   float64 translation[3], yaw, scales[3].  t_wo = (row-order sum of columns 9..11 over ALL rows) / rows;
+ *                                   translation = (t_wo + ... + t_wo, n_obs terms added one after the other) / n_obs, the mean of n_obs
+ *                                   equal poses that averaging_T_wos takes, and what init and bboxes_dl use; scales = (view-order sum of
+ *                                   columns 6..8 over the views) / n_obs; yaw = atan2(sum sin, sum cos) of column 12 over the views
+ *   bboxes_dl    [dev] [n_obj][8][3] float64 get_3d_box(scales, rotz(yaw), translation)
+ *   status       [dev] [n_obj]      0;  ODAM_SQ_PREPARE_NO_VIEW (1): no view -- cls, n_obs = n_valid = 0 and status are written, nothing
+ *                                   else;  ODAM_SQ_PREPARE_BAD_CLASS (2): a class value is not an integer in 0..63 -- cls = -1, everything
+ *                                   else as for status 0;  ODAM_SQ_PREPARE_TOO_MANY_ROWS (3): decided from row_off alone, no row is read --
+ *                                   cls = -1, n_obs = n_valid = 0, nothing else written.  1 goes before 2.
+ * Per view, written from row_off[o] on in image order; the words of a track beyond its n_obs views are not touched:
+ *   view_img     [dev] [R]          image index
+ *   view_row     [dev] [R]          row inside the track (0-based) the view came from
+ *   tgt          [dev] [R][4]       float32 edge value where it is a constraint, else 0
+ *   mask         [dev] [R][4]       1 / 0
+ *   P            [dev] [R][12]      float32(P_cws[image])
+ *   valid        [dev] [R]          1: at least one constrained edge
+ */
+#define ODAM_SQ_DUAL_QUADRIC 3
+#define ODAM_SQ_PREPARE_MAX_ROWS 16384
+#define ODAM_SQ_PREPARE_NO_VIEW 1
+#define ODAM_SQ_PREPARE_BAD_CLASS 2
+#define ODAM_SQ_PREPARE_TOO_MANY_ROWS 3
+int odam_sq_prepare_batch(odam_sq_ctx* ctx, int n_obj, const int* row_off, const double* rows, int max_rows, int n_img,
+                          const long long* img_ids, const int* img_order, const double* P_cws, double img_w, double img_h,
+                          double thr, int representation, int* cls, int* n_obs, int* n_valid, float* init, float* half_dims,
+                          double* pose, double* bboxes_dl, int* status, int* view_img, int* view_row, float* tgt, float* mask,
+                          float* P, int* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

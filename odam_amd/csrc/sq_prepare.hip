@@ -1,0 +1,325 @@
+// sq_prepare.hip -- the prelude of a fit pass on the device (include/odam_sq.h, odam_sq_prepare_batch): the views, constraint rows and
+// initial shape of every track in one launch.  Restates, for sequences whose frame ids are all different (likojack/ODAM):
+//   src/utils/tracking_gt_utils.py:145-211, 59-66   load_pred_object, averaging_T_wos
+//   src/super_quadric/quadric_helper.py:69-109      bbox_to_lines
+//   src/scripts/run_multi_view.py:44-62             the views with a constrained edge, get_3d_box of the detector's pose
+//   src/super_quadric/sq_libs.py:353-371, 41-58     the initial parameters of both optimisers
+//
+// One workgroup per track, no device-wide barrier, no persistent loop.  Row i of the track becomes the 64-bit key
+// (image index << 32 | i), or all ones when its frame id names no image; a bitonic sort of the keys in LDS, sized to the track's own
+// power of two, puts the rows in image order with the lowest row of a frame id first, so a sorted entry is a view exactly when it is
+// not all ones and its image differs from its left neighbour's.  A block scan of those flags gives every view its place, and the
+// thread that owns a view writes its per-view outputs.
+//
+// Sums whose bits are part of the contract are taken by single lanes in the stated order (lanes 0..2 of wave 0: columns 9..11 over all
+// rows in row order; lanes 3..5: columns 6..8 over the views in view order; the loads are issued eight ahead of the additions).  The
+// sums of sin / cos that decide the yaw are a per-thread, per-wave (XOR butterfly), per-workgroup (wave order) reduction: fixed, so
+// results repeat from launch to launch, but not the order of a host sum.  The class is a median over integers 0..63: a histogram.
+// Compiled with -ffp-contract=off: every product and sum is rounded on its own.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/odam_sq.h"
+#include "odam_err.h"
+
+namespace {
+
+constexpr unsigned long long NO_VIEW = ~0ull;
+constexpr int MAX_WAVES = 16;
+constexpr int N_CLASS = 64;
+
+struct PrepArgs {
+    const int* row_off;
+    const double* rows;
+    const long long* img_ids;
+    const int* img_order;
+    const double* P_cws;
+    int n_obj, n_img, cap, representation;      // cap: keys the launch's LDS holds
+    double img_w, img_h, thr;
+    int *cls, *n_obs, *n_valid;
+    float *init, *half_dims;
+    double *pose, *bboxes_dl;
+    int* status;
+    int *view_img, *view_row;
+    float *tgt, *mask, *P;
+    int* valid;
+};
+
+__device__ inline int wave_sum(int x) {
+    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
+    return x;
+}
+
+__device__ inline double wave_sum(double x) {
+    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
+    return x;
+}
+
+__device__ inline bool is_view(const unsigned long long* keys, int j) {
+    const unsigned long long k = keys[j];
+    return k != NO_VIEW && (j == 0 || (unsigned)(keys[j - 1] >> 32) != (unsigned)(k >> 32));
+}
+
+__global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+    __shared__ int s_hist[N_CLASS];
+    __shared__ int s_bad;
+    __shared__ int s_wcnt[MAX_WAVES], s_wvalid[MAX_WAVES];
+    __shared__ double s_wsin[MAX_WAVES], s_wcos[MAX_WAVES];
+    __shared__ double s_mean[6];      // translation[3], scales[3]
+    __shared__ double s_yaw;
+
+    const int obj = blockIdx.x;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const int lane = tid & 63, wave = tid >> 6, n_waves = T >> 6;
+    const int r0 = A.row_off[obj];
+    const int n = A.row_off[obj + 1] - r0;
+    // both refusals are workgroup-uniform and come before any row is read
+    if (n > A.cap || n <= 0) {
+        if (tid == 0) {
+            A.cls[obj] = -1;
+            A.n_obs[obj] = 0;
+            A.n_valid[obj] = 0;
+            A.status[obj] = n > A.cap ? ODAM_SQ_PREPARE_TOO_MANY_ROWS : ODAM_SQ_PREPARE_NO_VIEW;
+        }
+        return;
+    }
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;      // <= cap: cap is a power of two
+    const double* rows = A.rows + (size_t)r0 * 14;
+
+    if (tid < N_CLASS) s_hist[tid] = 0;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+
+    // keys and the class histogram
+    for (int i = tid; i < n2; i += T) {
+        unsigned long long key = NO_VIEW;
+        if (i < n) {
+            const double f = rows[(size_t)i * 14 + 0];
+            if (f > -2147483649.0 && f < 2147483648.0) {      // truncates into int32 (NaN fails both)
+                const long long id = (long long)(int)f;
+                int lo = 0, hi = A.n_img;                      // first entry >= id
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (A.img_ids[mid] < id) lo = mid + 1; else hi = mid;
+                }
+                if (lo < A.n_img && A.img_ids[lo] == id) {
+                    const int img = A.img_order[lo];
+                    if (img >= 0 && img < A.n_img) key = ((unsigned long long)(unsigned)img << 32) | (unsigned)i;
+                }
+            }
+            const double c = rows[(size_t)i * 14 + 1];
+            if (c >= 0.0 && c <= (double)(N_CLASS - 1) && c == floor(c)) atomicAdd(&s_hist[(int)c], 1);
+            else atomicOr(&s_bad, 1);
+        }
+        keys[i] = key;
+    }
+    __syncthreads();
+
+    // bitonic sort, ascending
+    for (int k = 2; k <= n2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int idx = tid; idx < (n2 >> 1); idx += T) {
+                const int a = ((idx & ~(j - 1)) << 1) | (idx & (j - 1));
+                const int b = a | j;
+                const unsigned long long ka = keys[a], kb = keys[b];
+                const bool up = (a & k) == 0;
+                if ((ka > kb) == up) { keys[a] = kb; keys[b] = ka; }
+            }
+            __syncthreads();
+        }
+
+    // every thread owns a run of L sorted entries; views in front of it = where its own views go
+    const int L = n2 > T ? n2 / T : 1;
+    const int j0 = tid * L;
+    const int j1 = j0 < n ? (j0 + L < n ? j0 + L : n) : j0;      // entries past n are all ones
+    int cnt = 0;
+    for (int j = j0; j < j1; j++) cnt += is_view(keys, j) ? 1 : 0;
+    int incl = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) s_wcnt[wave] = incl;
+    __syncthreads();
+    int base = incl - cnt, total = 0;
+    for (int w = 0; w < n_waves; w++) {
+        if (w < wave) base += s_wcnt[w];
+        total += s_wcnt[w];
+    }
+    const int n_obs = total;
+
+    // per-view outputs
+    const double lim[4] = {A.img_w, A.img_w, A.img_h, A.img_h};
+    const int col[4] = {2, 4, 3, 5};      // x_min, x_max, y_min, y_max
+    int my_valid = 0;
+    double my_sin = 0.0, my_cos = 0.0;
+    int p = base;
+    for (int j = j0; j < j1; j++) {
+        if (!is_view(keys, j)) continue;
+        const unsigned long long key = keys[j];
+        const int img = (int)(key >> 32), i = (int)(key & 0xffffffffu);
+        const size_t g = (size_t)r0 + (size_t)p;
+        const double* row = rows + (size_t)i * 14;
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const double v = row[col[e]];
+            const bool m = v > A.thr && v < lim[e] - A.thr;
+            A.mask[g * 4 + e] = m ? 1.0f : 0.0f;
+            A.tgt[g * 4 + e] = m ? (float)v : 0.0f;
+            any = any || m;
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) A.P[g * 12 + k] = (float)A.P_cws[(size_t)img * 12 + k];
+        A.view_img[g] = img;
+        A.view_row[g] = i;
+        A.valid[g] = any ? 1 : 0;
+        my_valid += any ? 1 : 0;
+        const double a = row[12];
+        my_sin = my_sin + sin(a);
+        my_cos = my_cos + cos(a);
+        p++;
+    }
+    const int wv = wave_sum(my_valid);
+    const double ws = wave_sum(my_sin), wc = wave_sum(my_cos);
+    if (lane == 0) { s_wvalid[wave] = wv; s_wsin[wave] = ws; s_wcos[wave] = wc; }
+
+    // the sums in stated order: wave 0, lanes 0..2 all rows (columns 9..11), lanes 3..5 the views (columns 6..8)
+    if (wave == 0) {
+        const bool all_rows = lane < 3;
+        const int c = all_rows ? 9 + lane : 3 + lane;
+        double s = 0.0;
+        bool have = false;
+        if (lane < 6) {
+            for (int jb = 0; jb < n; jb += 8) {
+                double v[8];
+                bool use[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const int j = jb + k;
+                    use[k] = false;
+                    v[k] = 0.0;
+                    if (j < n) {
+                        int i = j;
+                        if (all_rows) use[k] = true;
+                        else if (is_view(keys, j)) { use[k] = true; i = (int)(keys[j] & 0xffffffffu); }
+                        if (use[k]) v[k] = rows[(size_t)i * 14 + c];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    if (use[k]) { s = have ? s + v[k] : v[k]; have = true; }      // a sum starts with its first term, as np.add.reduce
+            }
+            if (all_rows) {
+                const double t_wo = s / (double)n;
+                if (n_obs > 0) {      // the mean of n_obs equal vectors, added one after the other
+                    double acc = t_wo;
+                    for (int k = 1; k < n_obs; k++) acc = acc + t_wo;
+                    s_mean[lane] = acc / (double)n_obs;
+                }
+            } else if (n_obs > 0) {
+                s_mean[lane] = s / (double)n_obs;
+            }
+        }
+    }
+    __syncthreads();
+
+    if (tid == 0) {
+        // class: median over the histogram
+        int cls = -1;
+        if (!s_bad) {
+            const int ra = (n - 1) >> 1, rb = n >> 1;      // ranks of the two middle values (equal for an odd count)
+            int seen = 0, va = -1, vb = -1;
+            for (int c = 0; c < N_CLASS; c++) {
+                seen += s_hist[c];
+                if (va < 0 && seen > ra) va = c;
+                if (vb < 0 && seen > rb) vb = c;
+            }
+            cls = (va + vb) >> 1;      // int((a + b) / 2) of non-negative integers
+        }
+        int nv = 0;
+        double S = 0.0, C = 0.0;
+        for (int w = 0; w < n_waves; w++) { nv += s_wvalid[w]; S = S + s_wsin[w]; C = C + s_wcos[w]; }
+        A.cls[obj] = cls;
+        A.n_obs[obj] = n_obs;
+        A.n_valid[obj] = nv;
+        A.status[obj] = n_obs == 0 ? ODAM_SQ_PREPARE_NO_VIEW : (s_bad ? ODAM_SQ_PREPARE_BAD_CLASS : 0);
+        if (n_obs > 0) {
+            const double yaw = atan2(S, C);
+            s_yaw = yaw;
+            double* pose = A.pose + (size_t)obj * 7;
+            pose[0] = s_mean[0]; pose[1] = s_mean[1]; pose[2] = s_mean[2];
+            pose[3] = yaw;
+            pose[4] = s_mean[3]; pose[5] = s_mean[4]; pose[6] = s_mean[5];
+            if (A.representation == ODAM_SQ_DUAL_QUADRIC) {
+                float* o = A.init + (size_t)obj * 5;
+                o[0] = (float)s_mean[0]; o[1] = (float)s_mean[1]; o[2] = (float)s_mean[2];
+                o[3] = (float)yaw;
+                o[4] = 1.0f;
+                float* h = A.half_dims + (size_t)obj * 3;
+                h[0] = (float)(s_mean[3] / 2.0); h[1] = (float)(s_mean[4] / 2.0); h[2] = (float)(s_mean[5] / 2.0);
+            } else {
+                float* o = A.init + (size_t)obj * 9;
+                o[0] = (float)s_mean[0]; o[1] = (float)s_mean[1]; o[2] = (float)s_mean[2];
+                o[3] = (float)yaw;
+                o[4] = (float)sqrt(s_mean[3] / 2.0); o[5] = (float)sqrt(s_mean[4] / 2.0); o[6] = (float)sqrt(s_mean[5] / 2.0);
+                const float shape = A.representation == ODAM_SQ_CUBE ? -10000.0f : -0.0f;
+                o[7] = shape; o[8] = shape;
+            }
+        }
+    }
+    __syncthreads();
+
+    // get_3d_box: corner k from thread k
+    if (tid < 8 && n_obs > 0) {
+        const double yaw = s_yaw;
+        const double c = cos(yaw), s = sin(yaw);
+        const double hl = s_mean[3] / 2.0, hw = s_mean[4] / 2.0, hh = s_mean[5] / 2.0;
+        const int k = tid;
+        const double x = (k & 2) ? -hl : hl;                       // l/2, l/2, -l/2, -l/2, ...
+        const double y = (((k + 1) & 2) ? -hw : hw);               // w/2, -w/2, -w/2, w/2, ...
+        const double z = (k & 4) ? -hh : hh;
+        double* o = A.bboxes_dl + ((size_t)obj * 8 + k) * 3;
+        o[0] = ((c * x + (-s) * y) + 0.0 * z) + s_mean[0];
+        o[1] = ((s * x + c * y) + 0.0 * z) + s_mean[1];
+        o[2] = ((0.0 * x + 0.0 * y) + 1.0 * z) + s_mean[2];
+    }
+}
+
+}  // namespace
+
+extern "C" int odam_sq_prepare_batch(odam_sq_ctx* ctx, int n_obj, const int* row_off, const double* rows, int max_rows, int n_img,
+                                     const long long* img_ids, const int* img_order, const double* P_cws, double img_w, double img_h,
+                                     double thr, int representation, int* cls, int* n_obs, int* n_valid, float* init, float* half_dims,
+                                     double* pose, double* bboxes_dl, int* status, int* view_img, int* view_row, float* tgt, float* mask,
+                                     float* P, int* valid, void* stream) {
+    if (!ctx || !row_off || !rows || !img_ids || !img_order || !P_cws || !cls || !n_obs || !n_valid || !init || !pose || !bboxes_dl ||
+        !status || !view_img || !view_row || !tgt || !mask || !P || !valid)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_batch: null pointer");
+    if (representation < 0 || representation > ODAM_SQ_DUAL_QUADRIC)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_batch: representation outside 0..3");
+    if (representation == ODAM_SQ_DUAL_QUADRIC && !half_dims)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_batch: half_dims is null for the dual quadric");
+    if (n_obj < 0 || n_img < 0 || max_rows < 1) return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_batch: bad size");
+    if (n_obj == 0) return ODAM_OK;
+    int cap = 1;
+    while (cap < max_rows && cap < ODAM_SQ_PREPARE_MAX_ROWS) cap <<= 1;
+    int threads = cap / 2;
+    threads = threads < 64 ? 64 : (threads > 1024 ? 1024 : threads);
+    const size_t lds = sizeof(unsigned long long) * (size_t)cap;
+    if (lds > 48 * 1024)
+        ODAM_HIP(hipFuncSetAttribute((const void*)sq_prepare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    PrepArgs A{};
+    A.row_off = row_off; A.rows = rows; A.img_ids = img_ids; A.img_order = img_order; A.P_cws = P_cws;
+    A.n_obj = n_obj; A.n_img = n_img; A.cap = cap; A.representation = representation;
+    A.img_w = img_w; A.img_h = img_h; A.thr = thr;
+    A.cls = cls; A.n_obs = n_obs; A.n_valid = n_valid; A.init = init; A.half_dims = half_dims; A.pose = pose; A.bboxes_dl = bboxes_dl;
+    A.status = status; A.view_img = view_img; A.view_row = view_row; A.tgt = tgt; A.mask = mask; A.P = P; A.valid = valid;
+    hipLaunchKernelGGL(sq_prepare_kernel, dim3((unsigned)n_obj), dim3((unsigned)threads), lds, (hipStream_t)stream, A);
+    ODAM_HIP(hipGetLastError());
+    return ODAM_OK;
+}

@@ -13,7 +13,10 @@ the result):
   src/super_quadric/quadric_helper.py:69-109  bbox_to_lines  -> _edge_lines
   src/utils/box_utils.py:286-308          get_3d_box
   src/utils/box_utils.py:319-410          compute_oriented_bbox (qhull hull + rotating calipers)
+With prelude="device" the part before the launch is one launch too (_device_prelude -> SqFitter.prepare, include/odam_sq.h
+odam_sq_prepare_batch); the host prelude above is the default and the fallback.
 """
+import logging
 import math
 
 import numpy as np
@@ -22,7 +25,8 @@ from scipy.spatial.transform import Rotation
 
 from . import sq as _sq
 
-EDGE_THRESHOLD = 20  # tracking_gt_utils.py:199
+EDGE_THRESHOLD = _sq.EDGE_THRESHOLD  # tracking_gt_utils.py:199
+_log = logging.getLogger(__name__)
 
 
 def rotz(t):  # box_utils.py:311-316
@@ -168,17 +172,16 @@ def _object_constraints(track, frame_to_img, img_h, img_w, thr=EDGE_THRESHOLD, w
 
 
 class _UniqueFrames:
-    """frame id -> image index for a sequence whose frame ids are all different: ids sorted, order[i] = image index of ids[i]"""
+    """frame id -> image index for a sequence whose frame ids are all different: ids sorted, order[i] = image index of ids[i] --
+    sq.frame_tables, the tables the prelude kernel searches, under sq.unique_frame_ids, the one statement of the rule"""
 
     def __init__(self, img_names):
-        names = np.asarray([int(f) for f in img_names], np.int64)
-        self.order = np.argsort(names, kind="stable").astype(np.int64)
-        self.ids = names[self.order]
+        self.ids, order = _sq.frame_tables(img_names)
+        self.order = order.astype(np.int64)
 
     @staticmethod
     def applies(img_names):
-        names = np.asarray([int(f) for f in img_names], np.int64)
-        return len(names) > 0 and len(np.unique(names)) == len(names) and np.abs(names).max() < 2 ** 31
+        return _sq.unique_frame_ids(img_names) is not None
 
 
 def averaging_T_wos_batch(R_list, t_list):
@@ -260,16 +263,20 @@ def default_fitter(device="cuda:0"):
     return _DEFAULT_FITTER[device]
 
 
-def _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, fit_mask, n_iters, fitter, return_params):
+def _finish_dual(tracks, pre, n_iters, fitter, return_params):
     """The fit and result half of optim_process for representation "dual_quadric": all eligible objects in one fit_dual call
     (an object whose discriminant goes negative raises AssertionError there, as sq_libs.py:129,136 does), DualQuadric results,
-    bboxes_qc from compute_oriented_bbox of the 2500 ellipsoid points (run_multi_view.py:66-67) through the native box path."""
+    bboxes_qc from compute_oriented_bbox of the 2500 ellipsoid points (run_multi_view.py:66-67) through the native box path.
+    `pre`: what _host_prelude / _device_prelude return."""
     n_objs = len(tracks)
+    fit_ids = pre["fit_ids"]
+    out = None
+    if fit_ids:
+        out = fitter.fit_dual(pre["fit_init"][0], pre["fit_init"][1], pre["fit_counts"], pre["P"], pre["tgt"], pre["mask"], n_iters=n_iters)
+    inits, bboxes_dl = pre["host"]()
     params = {i: inits[i][0] for i in range(n_objs)}
     Qs = {}
     if fit_ids:
-        out = fitter.fit_dual(np.stack([inits[i][0] for i in fit_ids]), np.stack([inits[i][1] for i in fit_ids]), fit_counts,
-                              np.concatenate(fit_P), np.concatenate(fit_tgt), np.concatenate(fit_mask), n_iters=n_iters)
         fp, fq = out["params"].cpu().numpy(), out["Q"].cpu().numpy()
         for j, i in enumerate(fit_ids):
             params[i] = fp[j]
@@ -314,19 +321,10 @@ def _check_resume(resume, representation, n_objs):
     return resume["state"], ids
 
 
-def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representation, prior, n_iters, n_views,
-                  fitter=None, return_params=False, resume=None, return_state=False):
-    """run_multi_view.py:22-76 with the per-object fits batched on the GPU.
-
-    Resumable (SqFitter.fit's state): with return_state the dict also holds "state" = {"state": [k, 32] rows, "track_ids": the k
-    tracks fitted, "representation"}; passed back as `resume`, every track in it that is fitted again continues from its row for
-    n_iters MORE steps on its current views (the constraint rows are rebuilt from the track as always), every other track starts
-    cold.  State is keyed by track index: valid while association only appends tracks, invalid after merge_process."""
-    fitter = fitter or default_fitter()
+def _host_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prior, n_views):
+    """The prelude of a fit pass on the host, per track (run_multi_view.py:44-62): class, detector box, initial parameters, and the
+    packed constraint rows of the tracks with at least n_views constrained views."""
     n_objs = len(tracks)
-    res_state = res_ids = None
-    if resume is not None or return_state:
-        res_state, res_ids = _check_resume(resume, representation, n_objs)
     frame_to_img = _frame_index(img_names)
     P_all = np.asarray(P_cws)
 
@@ -359,17 +357,126 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
             fit_tgt.append(tgt[valid])
             fit_mask.append(mask[valid])
             fit_counts.append(int(valid.sum()))
+    pre = {"classes": classes, "fit_ids": fit_ids, "fit_counts": fit_counts, "host": lambda: (inits, bboxes_dl)}
+    if fit_ids:
+        if representation == "dual_quadric":
+            pre["fit_init"] = (np.stack([inits[i][0] for i in fit_ids]), np.stack([inits[i][1] for i in fit_ids]))
+        else:
+            pre["fit_init"] = np.stack([inits[i] for i in fit_ids])
+        pre["P"], pre["tgt"], pre["mask"] = np.concatenate(fit_P), np.concatenate(fit_tgt), np.concatenate(fit_mask)
+    return pre
+
+
+def _device_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prior, n_views, fitter):
+    """The same prelude through SqFitter.prepare: ONE concatenate of the tracks' first 14 columns, one upload, one launch for all
+    tracks, one small copy back (class, view counts, status); the tracks to fit are picked on the host from the counts and their
+    constrained views are gathered on the device into the packed rows fit / fit_dual take as device tensors.  Returns the dict of
+    _host_prelude, or None where this call has to take the host path: frame ids that are not all different, no track, a track
+    the kernel refuses (no view, a class that is no integer in 0..63, more than sq.PREPARE_MAX_ROWS rows), or a track that is not a
+    float64 array of at least 14 columns -- the host path then raises what it always raised.  Class, views, counts, tgt, mask, P, translate and scales are the host path's bits; the yaw is the closed form
+    atan2(sum sin, sum cos) of the same mean rotation: a float32 init row can differ by one unit in the last place of
+    its angle, bboxes_dl in the last digits of a float64."""
+    import torch
+    n_objs = len(tracks)
+    if n_objs == 0 or not _UniqueFrames.applies(img_names):
+        return None
+    arrs = [np.asarray(t) for t in tracks]
+    if any(a.ndim != 2 or a.shape[1] < 14 or a.dtype != np.float64 for a in arrs):
+        return None      # the kernel reads float64 rows of 14 columns; the host path computes in the dtype it is given, or raises
+    lens = np.array([len(a) for a in arrs], np.int64)
+    offs = np.zeros(n_objs + 1, np.int64)
+    offs[1:] = np.cumsum(lens)
+    rows = np.concatenate([a[:, :14] for a in arrs]).astype(np.float64, copy=False)
+    prep = fitter.prepare(rows, offs, img_names, P_cws, img_h, img_w, representation)
+    if prep["status"].any():
+        return None
+    dual = representation == "dual_quadric"
+    classes = [int(c) for c in prep["cls"]]
+    if prior and not dual:
+        for c in classes:
+            if c not in _sq.CLASS_MAPPER:
+                raise KeyError(c)  # sq_libs.py:464, where the host path raises it: at the first such track
+    fit = prep["n_valid"] >= n_views
+    fit_ids = [int(i) for i in np.flatnonzero(fit)]
+    fit_counts = [int(c) for c in prep["n_valid"][fit]]
+
+    def host():      # the rows of the result dict: one copy each, taken after the fit has been launched
+        box = prep["bboxes_dl"].cpu().numpy()
+        init = prep["init"].cpu().numpy()
+        if dual:
+            half = prep["half_dims"].cpu().numpy()
+            return [(init[i], half[i]) for i in range(n_objs)], [box[i] for i in range(n_objs)]
+        return [init[i] for i in range(n_objs)], [box[i] for i in range(n_objs)]
+    pre = {"classes": classes, "fit_ids": fit_ids, "fit_counts": fit_counts, "host": host}
+    if fit_ids:
+        dev = prep["valid"].device
+        R, K = len(rows), int(sum(fit_counts))
+        # place of every constrained view of a fitted track among the packed rows: a running count, no read-back.  A track has
+        # n_obs <= its rows views (a frame id can repeat or name no image); prepare hands "valid" out as 0 in the words past them,
+        # so exactly K rows are selected
+        sel = (prep["valid"] != 0) & torch.from_numpy(np.repeat(fit, lens)).to(dev)
+        pos = torch.cumsum(sel, 0) - 1
+        idx = torch.empty(K + 1, device=dev, dtype=torch.int64)      # slot K takes every row that is not packed
+        idx.scatter_(0, torch.where(sel, pos, torch.full_like(pos, K)), torch.arange(R, device=dev))
+        idx = idx[:K]
+        pre["P"], pre["tgt"], pre["mask"] = prep["P"].index_select(0, idx), prep["tgt"].index_select(0, idx), prep["mask"].index_select(0, idx)
+        ids_dev = torch.as_tensor(fit_ids, device=dev)
+        if dual:
+            pre["fit_init"] = (prep["init"].index_select(0, ids_dev), prep["half_dims"].index_select(0, ids_dev))
+        else:
+            p0 = prep["init"].index_select(0, ids_dev)
+            pre["fit_init"] = p0
+
+            def cold_state():      # sq.cold_state on the device
+                st = torch.zeros(len(fit_ids), _sq.STATE_FLOATS, device=dev, dtype=torch.float32)
+                st[:, 0:9] = p0
+                st[:, 27:30] = p0[:, 4:7]
+                st[:, 31] = _sq.REPRESENTATIONS[representation]
+                return st
+            pre["cold_state"] = cold_state
+    return pre
+
+
+def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representation, prior, n_iters, n_views,
+                  fitter=None, return_params=False, resume=None, return_state=False, prelude="host"):
+    """run_multi_view.py:22-76 with the per-object fits batched on the GPU.
+
+    Resumable (SqFitter.fit's state): with return_state the dict also holds "state" = {"state": [k, 32] rows, "track_ids": the k
+    tracks fitted, "representation"}; passed back as `resume`, every track in it that is fitted again continues from its row for
+    n_iters MORE steps on its current views (the constraint rows are rebuilt from the track as always), every other track starts
+    cold.  State is keyed by track index: valid while association only appends tracks, invalid after merge_process.
+
+    prelude: "host" (default) builds the constraint rows and initial shapes per track in numpy / scipy; "device" builds them for
+    all tracks in one launch (_device_prelude, SqFitter.prepare) and falls back to the host path for this call, with one debug log
+    line, where that does not apply: frame ids that are not all different, a track the kernel refuses (no view, a class that is no
+    integer in 0..63, more than 16384 rows), no track, or a track that is not a float64 array of at least 14 columns."""
+    if prelude not in ("host", "device"):
+        raise ValueError(f'prelude must be "host" or "device", got {prelude!r}')
+    fitter = fitter or default_fitter()
+    n_objs = len(tracks)
+    res_state = res_ids = None
+    if resume is not None or return_state:
+        res_state, res_ids = _check_resume(resume, representation, n_objs)
+    pre = None
+    if prelude == "device":
+        pre = _device_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prior, n_views, fitter)
+        if pre is None:
+            _log.debug("optim_process: the device prelude does not apply to this call (%d tracks), taking the host path", n_objs)
+    if pre is None:
+        pre = _host_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prior, n_views)
+    classes, fit_ids, fit_counts = pre["classes"], pre["fit_ids"], pre["fit_counts"]
 
     if representation == "dual_quadric":
-        return _finish_dual(tracks, inits, bboxes_dl, fit_ids, fit_counts, fit_P, fit_tgt, fit_mask, n_iters, fitter, return_params)
-    params = {i: inits[i] for i in range(n_objs)}
+        return _finish_dual(tracks, pre, n_iters, fitter, return_params)
     points = {}
     state_out = None
+    out = None
     if fit_ids:
         more = {}
         if resume is not None or return_state:
             import torch
-            st = torch.from_numpy(_sq.cold_state(np.stack([inits[i] for i in fit_ids]), representation))
+            # rows of fits that have not begun: the device prelude makes them where its init rows are
+            st = pre["cold_state"]() if "cold_state" in pre else torch.from_numpy(_sq.cold_state(pre["fit_init"], representation))
             if res_ids is not None and len(res_ids):
                 row_of = {int(t): j for j, t in enumerate(res_ids)}
                 dst = [j for j, i in enumerate(fit_ids) if i in row_of]
@@ -378,10 +485,12 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
                     st = st.to(rs.device)
                     st[torch.as_tensor(dst, device=rs.device)] = rs[torch.as_tensor([row_of[fit_ids[j]] for j in dst], device=rs.device)].to(torch.float32)
             more = dict(state=st, want_state=bool(return_state))
-        out = fitter.fit(np.stack([inits[i] for i in fit_ids]), [classes[i] for i in fit_ids], fit_counts,
-                         np.concatenate(fit_P), np.concatenate(fit_tgt), np.concatenate(fit_mask),
+        out = fitter.fit(pre["fit_init"], [classes[i] for i in fit_ids], fit_counts, pre["P"], pre["tgt"], pre["mask"],
                          n_iters=n_iters, representation=representation, prior=bool(prior), want_points=True, **more)
         state_out = out.get("state") if return_state else None
+    inits, bboxes_dl = pre["host"]()
+    params = {i: inits[i] for i in range(n_objs)}
+    if fit_ids:
         fp = out["params"].cpu().numpy()
         fpts = out["points"].cpu().numpy()
         for j, i in enumerate(fit_ids):

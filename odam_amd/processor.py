@@ -106,6 +106,7 @@ class OdamProcess:
         self.fitter = fitter
         self.refine_fitter = None   # refine(): its own context, with a bias-correction table long enough for a whole scan (REFINE_MAX_ITERS)
         self._refine_state = None   # refine(): what multi_view.optim_process(return_state=True) returned last, keyed by track index
+        self.device_prelude = False  # optim_process / refine with prelude=None: True builds the fits' constraint rows on the device (multi_view.optim_process, prelude="device")
         self.logger = logging.getLogger('OdamProcess')
 
     # `tracks` is the reference's attribute (src/processor.py:300; a list of [n, 82] arrays, index = track id).  The fast path of
@@ -735,13 +736,14 @@ class OdamProcess:
 
     REFINE_MAX_ITERS = 4000     # steps one track can take over all refine() calls of a sequence (rows of the context's Adam table)
 
-    def refine(self, n_iters=50, return_params=False):
+    def refine(self, n_iters=50, return_params=False, prelude=None):
         """The online call: current shapes of the live tracks while the scan is running.  Fits every track with enough views for
         n_iters steps, CONTINUING every track an earlier refine() of this sequence fitted (parameters, Adam moments, step count and
         the scales the prior is measured from are kept here, per track index) on the views it has now; a new track, or one that had
         too few views last time, starts cold.  Returns optim_process's dict.  Reads the tracks and nothing else: association, and
         optim_process at the end of the scan, go on as if it had never been called.  init_sequence clears the state, merge_process
-        drops it (track indices change there).  Not for representation "dual_quadric"."""
+        drops it (track indices change there).  Not for representation "dual_quadric".  prelude: "host", "device" (multi_view.optim_process), or
+        None for what self.device_prelude says."""
         if self.representation == "dual_quadric":
             raise ValueError('refine: the "dual_quadric" fit is not resumable')
         if self.refine_fitter is None:
@@ -750,7 +752,7 @@ class OdamProcess:
         out = multi_view.optim_process(self.tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                        self.representation, prior=True, n_iters=int(n_iters), n_views=10,
                                        fitter=self.refine_fitter, return_params=return_params,
-                                       resume=self._refine_state, return_state=True)
+                                       resume=self._refine_state, return_state=True, prelude=self._prelude(prelude))
         # (a track fitted once is fitted every time after: its views only grow, so the new rows cover the old ones)
         self._refine_state = out.pop("state")
         return out
@@ -793,13 +795,19 @@ class OdamProcess:
         from . import evaluate
         return evaluate.detections_ap(blk, cnt, other_blk, other_cnt, iou, ovthresh, use_07_metric, fitter=self._fitter())
 
-    def optim_process(self, tracks, return_params=False):
+    def _prelude(self, prelude):
+        if prelude is None:
+            return "device" if self.device_prelude else "host"
+        return prelude
+
+    def optim_process(self, tracks, return_params=False, prelude=None):
+        """prelude: "host", "device" (multi_view.optim_process), or None for what self.device_prelude says"""
         m = self.sequence_meta
         # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
         n_iters = 500 if self.representation == "dual_quadric" else 200
         return multi_view.optim_process(tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                         self.representation, prior=True, n_iters=n_iters, n_views=10,
-                                        fitter=self._fitter(), return_params=return_params)
+                                        fitter=self._fitter(), return_params=return_params, prelude=self._prelude(prelude))
 
     def optim_process_params(self, tracks):
         """optim_process + the fitted parameter rows and the fitted / not-fitted flags (what a rank sends to the others:

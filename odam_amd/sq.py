@@ -105,6 +105,40 @@ def _reproject_entry(name):
     return f
 
 
+# odam_sq_prepare_batch as include/odam_sq.h declares it (tests/test_sq_prepare_host.py holds the two together)
+_CD = ctypes.c_double
+PREPARE_ARGTYPES = [_VP, _CI, _VP, _VP, _CI, _CI, _VP, _VP, _VP, _CD, _CD, _CD, _CI] + [_VP] * 15
+PREPARE_MAX_ROWS = 16384      # ODAM_SQ_PREPARE_MAX_ROWS: rows of one track the prelude kernel sorts
+PREPARE_NO_VIEW, PREPARE_BAD_CLASS, PREPARE_TOO_MANY_ROWS = 1, 2, 3      # its status codes
+EDGE_THRESHOLD = 20           # tracking_gt_utils.py:199
+
+
+def _prepare_entry():
+    f = _lib.lib().odam_sq_prepare_batch
+    if f.argtypes is None:
+        f.argtypes, f.restype = PREPARE_ARGTYPES, ctypes.c_int
+    return f
+
+
+def unique_frame_ids(img_names):
+    """img_names as int64 where every frame id names ONE image -- at least one id, all different, inside int32 -- else None: the rule
+    under which multi_view._UniqueFrames and odam_sq_prepare_batch find a row's image by binary search"""
+    names = np.asarray([int(f) for f in img_names], np.int64)
+    if not len(names) or len(np.unique(names)) != len(names) or np.abs(names).max() >= 2 ** 31:
+        return None
+    return names
+
+
+def frame_tables(img_names):
+    """img_names -> (ids int64 ascending, order int32: image index of ids[i]), the two tables odam_sq_prepare_batch searches (and
+    multi_view._UniqueFrames holds); ValueError unless unique_frame_ids accepts the names"""
+    names = unique_frame_ids(img_names)
+    if names is None:
+        raise ValueError("prepare: the frame ids of img_names must be all different, inside int32, and at least one")
+    order = np.argsort(names, kind="stable")
+    return names[order], order.astype(np.int32)
+
+
 def cold_state(params0, representation):
     """[n, 32] float32 rows of fits that have not begun (include/odam_sq.h): what a track that starts cold gets inside a resumed call"""
     p = np.asarray(params0, np.float32).reshape(-1, 9)
@@ -303,6 +337,69 @@ class SqFitter:
         if want_state:
             out["state"] = st_out
         return out
+
+    def prepare(self, rows, row_offsets, img_names, P_cws, img_h, img_w, representation="super_quadric", thr=EDGE_THRESHOLD):
+        """The prelude of a fit pass for ALL tracks in one launch (include/odam_sq.h, odam_sq_prepare_batch): views, constraint rows,
+        class, detector box and initial parameters of every track.
+
+        rows [R, 14] float64: the first 14 columns of every track row, track after track; row_offsets [n + 1]: track o owns rows
+        row_offsets[o] .. row_offsets[o + 1] - 1 (numpy or torch, on the host or the device; offsets given on the host are checked
+        and size the launch, offsets on the device are taken as they are and the launch is sized for the largest track the kernel
+        takes -- nothing is read back for them); img_names: the frame id of every image, all different; P_cws [n_img, 3, 4].
+        Returns a dict: "cls", "n_obs", "n_valid", "status" [n] int32 numpy on the host -- ONE small copy, the only synchronisation
+        -- and device tensors "init" ([n, 9], or [n, 5] with "half_dims" [n, 3] for "dual_quadric"; else half_dims is None), "pose"
+        [n, 7] and "bboxes_dl" [n, 8, 3] float64, per view from row_offsets[o] on "view_img", "view_row", "valid" [R] int32, "tgt",
+        "mask" [R, 4], "P" [R, 12] float32, and "row_offsets" [n + 1] int32.  Rows of a per-track output whose status says it was
+        not written, and per-view words beyond a track's n_obs views (fewer than its rows where a frame id repeats or names no image),
+        are uninitialised memory -- except "valid", which is 0 there: (valid != 0) marks the constrained views among all R rows."""
+        dev = self.device
+        rep = REPRESENTATIONS[representation]
+        ids, order = frame_tables(img_names)
+        if torch.is_tensor(row_offsets) and row_offsets.is_cuda:
+            d_off = row_offsets.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+            max_rows = PREPARE_MAX_ROWS
+        else:
+            offs = np.asarray(row_offsets.numpy() if torch.is_tensor(row_offsets) else row_offsets).astype(np.int64).reshape(-1)
+            if len(offs) < 1 or offs[0] != 0 or (np.diff(offs) < 0).any() or offs[-1] != len(rows) or offs[-1] >= 2 ** 31:
+                raise ValueError(f"prepare: row_offsets must run from 0 to the {len(rows)} rows given without decreasing")
+            d_off = torch.from_numpy(offs.astype(np.int32)).to(dev)
+            max_rows = int(np.diff(offs).max()) if len(offs) > 1 else 1
+        n = d_off.shape[0] - 1
+        d_rows = self._as_dev(rows, torch.float64)
+        if d_rows.dim() != 2 or d_rows.shape[1] != 14:
+            raise ValueError(f"prepare: rows must be [R, 14], got {tuple(d_rows.shape)}")
+        R = d_rows.shape[0]
+        d_Pc = self._as_dev(P_cws, torch.float64).reshape(-1, 12)
+        if d_Pc.shape[0] != len(ids):
+            raise ValueError(f"prepare: {d_Pc.shape[0]} projections for {len(ids)} images")
+        d_ids, d_ord = torch.from_numpy(ids).to(dev), torch.from_numpy(order).to(dev)
+        ints = torch.empty(4, max(n, 1), device=dev, dtype=torch.int32)      # cls, n_obs, n_valid, status: read back in one copy
+        init = torch.empty(n, 5 if rep == 3 else 9, device=dev, dtype=torch.float32)
+        half = torch.empty(n, 3, device=dev, dtype=torch.float32) if rep == 3 else None
+        pose = torch.empty(n, 7, device=dev, dtype=torch.float64)
+        box = torch.empty(n, 8, 3, device=dev, dtype=torch.float64)
+        pad = max(R, 1)      # (an empty tensor has no pointer to pass)
+        view_img = torch.empty(pad, device=dev, dtype=torch.int32)
+        view_row = torch.empty(pad, device=dev, dtype=torch.int32)
+        valid = torch.zeros(pad, device=dev, dtype=torch.int32)      # 0 wherever the kernel writes no view: a mask over all R rows
+        tgt = torch.empty(pad, 4, device=dev, dtype=torch.float32)
+        mask = torch.empty(pad, 4, device=dev, dtype=torch.float32)
+        P = torch.empty(pad, 12, device=dev, dtype=torch.float32)
+        if n and R:
+            with torch.cuda.device(dev), self._lock:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_prepare_entry()(
+                    self._h, n, _lib.ptr(d_off), _lib.ptr(d_rows), max(max_rows, 1), len(ids), _lib.ptr(d_ids), _lib.ptr(d_ord), _lib.ptr(d_Pc),
+                    float(img_w), float(img_h), float(thr), rep, _lib.ptr(ints[0]), _lib.ptr(ints[1]), _lib.ptr(ints[2]), _lib.ptr(init),
+                    _lib.ptr(half), _lib.ptr(pose), _lib.ptr(box), _lib.ptr(ints[3]), _lib.ptr(view_img), _lib.ptr(view_row), _lib.ptr(tgt),
+                    _lib.ptr(mask), _lib.ptr(P), _lib.ptr(valid), ctypes.c_void_p(stream)), "odam_sq_prepare_batch")
+            h = ints[:, :n].cpu().numpy()
+        else:      # no row at all: every track is one without a view
+            h = np.zeros((4, n), np.int32)
+            h[0], h[3] = -1, PREPARE_NO_VIEW
+        return {"cls": h[0], "n_obs": h[1], "n_valid": h[2], "status": h[3], "init": init, "half_dims": half, "pose": pose, "bboxes_dl": box,
+                "view_img": view_img[:R], "view_row": view_row[:R], "valid": valid[:R], "tgt": tgt[:R], "mask": mask[:R], "P": P[:R],
+                "row_offsets": d_off}
 
     def last_launch(self):
         """shape of the newest fit launch (odam_sq_last_launch): grid, threads per workgroup, workgroups per object, longest-first flag"""
