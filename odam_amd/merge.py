@@ -130,9 +130,104 @@ def _merge_cluster(tracks, mask, img_names):
     return np.asarray(out)
 
 
-def merge_process(data, img_names, fitter=None):
+def _device_scene(data, img_names):
+    """what the device merge needs of one scene -- (tracks, rows14 of all tracks, boxes, classes) -- or None when the scene is one the
+    kernels do not restate and the host path has to take it: a single track (returned untouched by the reference: no image
+    filtering, no class change), more tracks than the clustering kernel holds, image names that are not all different integers
+    inside int32, a track that is not a float64 array of at least 14 columns, an empty track, tracks of different widths"""
+    from . import sq
+    tracks = data["tracks"]
+    n = len(tracks)
+    if n < 2 or n > sq.MERGE_MAX_TRACKS:
+        return None
+    try:
+        if sq.unique_frame_ids(img_names) is None or any(int(f) != f for f in img_names):
+            return None
+    except (TypeError, ValueError):
+        return None
+    for t in tracks:
+        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2 or t.shape[1] < 14 or t.shape[1] != tracks[0].shape[1] \
+                or len(t) == 0:
+            return None
+    cls = np.array([int(np.median(t[:, 1])) for t in tracks], np.int32)
+    boxes = np.asarray([np.asarray(b, np.float64) for b in data["bboxes_qc"]]).reshape(n, 8, 3)
+    return tracks, [t[:, :14] for t in tracks], boxes, cls
+
+
+def _device_merge(datas, img_names_list, fitter, want_rows14):
+    """the three device steps for the scenes _device_scene accepts: ONE IoU launch, ONE clustering launch, ONE assembly pass, ONE small
+    copy back.  Returns (scenes, picked, res, head): scenes[k] = _device_scene's answer or None, picked = indices of the scenes that
+    went to the device (in launch order), res = SqFitter.merge_assemble's dict, head = its "head" on the host."""
+    from . import evaluate
+    fitter = evaluate._default_fitter(fitter)
+    scenes = [_device_scene(d, names) for d, names in zip(datas, img_names_list)]
+    picked = [k for k, s in enumerate(scenes) if s is not None]
+    if not picked:
+        return scenes, picked, None, None
+    r = evaluate._iou_launch([scenes[k][2] for k in picked], [scenes[k][2] for k in picked], [scenes[k][3] for k in picked],
+                             [scenes[k][3] for k in picked], 2, fitter, False)
+    cl = fitter.merge_cluster(r["iou3d"], r["a_off"], r["pair_off"])
+    rows = np.concatenate([t for k in picked for t in scenes[k][1]])
+    row_off = np.concatenate([[0], np.cumsum([len(t) for k in picked for t in scenes[k][1]])])
+    res = fitter.merge_assemble(cl, r["a_off"], rows, row_off, [img_names_list[k] for k in picked], want_rows14=want_rows14)
+    return scenes, picked, res, res["head"].cpu().numpy()
+
+
+def merge_scenes(datas, img_names_list, fitter=None):
+    """merge_process for many scenes at once on the device: the IoU of all pairs of all scenes in one launch, the clustering of all
+    scenes in one launch (SqFitter.merge_cluster), the assembly of all merged tracks in one pass (SqFitter.merge_assemble).
+    datas: one optim_process dict per scene; img_names_list: one list of frame ids per scene.  Returns, per scene, the list of
+    merged [n, 82] tracks merge_process returns, decision for decision.  Only offsets, source-row indices and classes come back from
+    the device; the merged rows are gathered on the host from the caller's tracks.  A scene the kernels do not restate
+    (_device_scene), or one that comes back with a status (a class that is not an integer in 0..63, a frame id twice in one track,
+    more than 16384 rows in one cluster), goes down the host path for this call."""
+    if len(datas) != len(img_names_list):
+        raise ValueError("one list of image names per scene")
+    scenes, picked, res, head = _device_merge(datas, img_names_list, fitter, False)
+    out = [None] * len(datas)
+    if picked:
+        ns = len(picked)
+        n_out, status, n_total, r_total = head[:ns], head[ns:2 * ns], int(head[2 * ns]), int(head[2 * ns + 1])
+        off = res["out_off"][:n_total + 1].cpu().numpy()
+        src = res["out_src"][:r_total].cpu().numpy()
+        cls = res["out_cls"][:n_total].cpu().numpy()
+        o = base = 0
+        for q, k in enumerate(picked):
+            tracks = scenes[k][0]
+            if status[q] == 0:
+                allrows = np.concatenate(tracks)
+                merged = []
+                for i in range(o, o + int(n_out[q])):
+                    t = allrows[src[off[i]:off[i + 1]] - base]      # (fancy indexing: a copy, the caller's tracks stay as they were)
+                    t[:, 1] = cls[i]
+                    merged.append(t)
+                out[k] = merged
+            o += int(n_out[q])
+            base += sum(len(t) for t in tracks)
+    for k, m in enumerate(out):
+        if m is None:
+            out[k] = merge_process(datas[k], img_names_list[k], fitter)
+    return out
+
+
+def merge_packed(data, img_names, fitter=None):
+    """One scene merged on the device and left there, for callers that go straight into SqFitter.prepare: {"rows14" [R_out, 14]
+    float64 (column 1 = the merged class), "row_offsets" [n_out + 1] int32, "cls" [n_out] int32, "src" [R_out] int32 (indices into
+    np.concatenate(data["tracks"]))}, all device tensors; or None when the scene has to go down the host path (merge_scenes)."""
+    scenes, picked, res, head = _device_merge([data], [img_names], fitter, True)
+    if not picked or head[1] != 0:
+        return None
+    n_out, r_out = int(head[2]), int(head[3])
+    return {"rows14": res["rows14"][:r_out], "row_offsets": res["out_off"][:n_out + 1], "cls": res["out_cls"][:n_out],
+            "src": res["out_src"][:r_out]}
+
+
+def merge_process(data, img_names, fitter=None, on_device=False):
     """run_merge.py:79-130: data = optim_process output dict; returns the list of merged [n,82] tracks.  With a fitter the pair
-    costs come from the device (cost_matrix)."""
+    costs come from the device (cost_matrix); with on_device the clustering and the assembly too (merge_scenes: the same tracks,
+    decision for decision)."""
+    if on_device:
+        return merge_scenes([data], [img_names], fitter)[0]
     tracks = data["tracks"]
     n = len(tracks)
     if n == 1:

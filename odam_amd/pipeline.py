@@ -94,7 +94,7 @@ def _associate(proc, frame_ids, T_wcs, c0, rows):
 
 
 def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=0, device=None, force=False, stages=None, overlap=None,
-              device_select=False):
+              device_select=False, device_merge=False):
     """The driver loop of run_processor.py:70-83 for one scene on the ranks of the current process group.
 
     proc      OdamProcess after init_sequence (its detector is used unless `detect` is given; its associator and fitter always)
@@ -111,6 +111,8 @@ def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=
               runs, in chunk order on every rank; results are identical with and without (the same calls on the same data).
     device_select  with the default `detect` only: a rank's share goes through proc.detect_frames_packed -- threshold, NMS and the rows
               on the device -- and the packed block straight into the gather; the same detections, bit for bit.  Frames of one size.
+    device_merge   the track merge between the two fit passes clusters and assembles on the device too (proc.merge_process(out,
+              on_device=True)): the same merged tracks, decision for decision.
     Returns the second optim_process dict (what the reference pickles), identical on every rank; proc.tracks holds the
     unmerged tracks."""
     import sys
@@ -208,7 +210,7 @@ def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=
     s0 = time.perf_counter()
     out = sharded_optim(proc, proc.tracks, device, force)
     s1 = time.perf_counter()
-    merged = proc.merge_process(out)
+    merged = proc.merge_process(out, on_device=True) if device_merge else proc.merge_process(out)
     s2 = time.perf_counter()
     out2 = sharded_optim(proc, merged, device, force)
     t.update(fit1=s1 - s0, merge=s2 - s1, fit2=time.perf_counter() - s2)

@@ -726,12 +726,15 @@ class OdamProcess:
         return self._track_frames_iou(frame_ids, T_wcs, packed=(blk, cnt))
 
     # ---- back end (processor.py:347-368) -----------------------------------------------------------
-    def merge_process(self, data):
+    def merge_process(self, data, on_device=False):
+        """on_device: clustering and assembly on the device too (merge.merge_scenes); the same merged tracks"""
         self.logger.info("Merging tracks")
         if self._refine_state is not None:      # keyed by track index, and merging renumbers the tracks
             self.logger.info("Dropping the fit state of %d refined tracks: track indices change in merge_process",
                              len(self._refine_state["track_ids"]))
             self._refine_state = None
+        if on_device:
+            return merge.merge_process(data, self.usable_frames, fitter=self._fitter(), on_device=True)
         return merge.merge_process(data, self.usable_frames)
 
     REFINE_MAX_ITERS = 4000     # steps one track can take over all refine() calls of a sequence (rows of the context's Adam table)

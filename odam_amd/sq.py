@@ -120,6 +120,23 @@ def _prepare_entry():
     return f
 
 
+# odam_merge_cluster / odam_merge_assemble as include/odam_merge.h declares them (tests/test_track_merge_host.py holds them together)
+_LL = ctypes.c_longlong
+MERGE_ARGTYPES = {
+    "odam_merge_cluster": [_VP, _CI, _VP, _VP, _CI, _LL, _CI, _VP, _CD, _VP, _VP, _VP, _VP, _VP, _VP],
+    "odam_merge_assemble": [_VP, _CI, _VP, _CI, _VP, _VP, _VP, _VP, _VP, _CI, _CI, _VP, _VP, _VP, _CI] + [_VP] * 9,
+}
+MERGE_MAX_TRACKS = 1024       # ODAM_MERGE_MAX_TRACKS: tracks of one scene the clustering kernel takes
+MERGE_THRESHOLD = 0.95        # run_merge.py:121
+
+
+def _merge_entry(name):
+    f = getattr(_lib.lib(), name)
+    if f.argtypes is None:
+        f.argtypes, f.restype = MERGE_ARGTYPES[name], ctypes.c_int
+    return f
+
+
 def unique_frame_ids(img_names):
     """img_names as int64 where every frame id names ONE image -- at least one id, all different, inside int32 -- else None: the rule
     under which multi_view._UniqueFrames and odam_sq_prepare_batch find a row's image by binary search"""
@@ -400,6 +417,100 @@ class SqFitter:
         return {"cls": h[0], "n_obs": h[1], "n_valid": h[2], "status": h[3], "init": init, "half_dims": half, "pose": pose, "bboxes_dl": box,
                 "view_img": view_img[:R], "view_row": view_row[:R], "valid": valid[:R], "tgt": tgt[:R], "mask": mask[:R], "P": P[:R],
                 "row_offsets": d_off}
+
+    def _offsets_dev(self, off, dt):
+        """offsets given on the host -> (host int64 array, device tensor of dtype dt)"""
+        h = np.asarray(off.cpu().numpy() if torch.is_tensor(off) else off).astype(np.int64).reshape(-1)
+        if len(h) < 1 or h[0] != 0 or (np.diff(h) < 0).any():
+            raise ValueError("offsets must start at 0 and not decrease")
+        if dt == torch.int32 and h[-1] >= 2 ** 31:
+            raise _lib.OdamError(f"{h[-1]} entries in one call: the offsets are 32-bit")
+        return h, torch.from_numpy(h.astype(np.int32 if dt == torch.int32 else np.int64)).to(self.device)
+
+    def merge_cluster(self, iou3d, a_off, pair_off, threshold=MERGE_THRESHOLD):
+        """Average-linkage clustering of every scene's tracks in ONE launch (include/odam_merge.h, odam_merge_cluster): what
+        sklearn's AgglomerativeClustering(n_clusters=None, distance_threshold=threshold, metric="precomputed", linkage="average")
+        answers for the cost 1 - IoU, decision for decision.
+
+        iou3d [n_pairs] float64 on the device as evaluate.iou_scenes(boxes, boxes, cls, cls, gate=2) returns it, a_off / pair_off
+        its host offsets.  More than 1024 tracks in a scene raise (ODAM_E_LIMIT) before any launch.  Returns device tensors
+        "linkage" [n_tracks, 4] float64 (scene s: rows a_off[s] .. a_off[s+1]-2, scipy's layout), "labels" [n_tracks] int32,
+        "n_cluster", "status" [n_scene] int32, "cost" (the kernel's working copy of the costs: after the call no longer the cost
+        matrix) and "a_off" on the device.  Nothing is copied back."""
+        dev = self.device
+        ao, d_aoff = self._offsets_dev(a_off, torch.int32)
+        po, d_poff = self._offsets_dev(pair_off, torch.int64)
+        n_scene, n_tracks, n_pairs = len(ao) - 1, int(ao[-1]), int(po[-1])
+        if len(po) != len(ao) or not np.array_equal(np.diff(po), np.diff(ao) ** 2):
+            raise ValueError("merge_cluster: pair_off must hold n_s * n_s words for the n_s tracks of every scene")
+        d_iou = self._as_dev(iou3d, torch.float64).reshape(-1)
+        if d_iou.shape[0] != n_pairs:
+            raise ValueError(f"merge_cluster: {d_iou.shape[0]} IoU words for {n_pairs} pairs")
+        max_tracks = int(np.diff(ao).max()) if n_scene else 0
+        cost = torch.empty(max(n_pairs, 1), device=dev, dtype=torch.float64)
+        link = torch.empty(max(n_tracks, 1), 4, device=dev, dtype=torch.float64)
+        labels = torch.empty(max(n_tracks, 1), device=dev, dtype=torch.int32)
+        ints = torch.empty(2, max(n_scene, 1), device=dev, dtype=torch.int32)
+        if d_iou.shape[0] == 0:
+            d_iou = cost
+        with torch.cuda.device(dev), self._lock:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_merge_entry("odam_merge_cluster")(
+                self._h, n_scene, _lib.ptr(d_aoff), _lib.ptr(d_poff), n_tracks, n_pairs, max_tracks, _lib.ptr(d_iou), float(threshold),
+                _lib.ptr(cost), _lib.ptr(link), _lib.ptr(labels), _lib.ptr(ints[0]), _lib.ptr(ints[1]), ctypes.c_void_p(stream)),
+                "odam_merge_cluster")
+        return {"linkage": link[:n_tracks], "labels": labels[:n_tracks], "n_cluster": ints[0, :n_scene], "status": ints[1, :n_scene],
+                "cost": cost[:n_pairs], "a_off": d_aoff}
+
+    def merge_assemble(self, clusters, a_off, rows, row_offsets, img_names_list, want_rows14=True):
+        """The merged tracks of every cluster of every scene (include/odam_merge.h, odam_merge_assemble): merge.py::_merge_cluster on
+        the device, three launches.
+
+        clusters: what merge_cluster returned; a_off: its host offsets; rows [R, 14] float64 and row_offsets [n_tracks + 1] as
+        prepare takes them, the tracks of all scenes one after the other; img_names_list: the frame ids of every scene's images, all
+        different inside a scene.  Returns device tensors "out_off" [n_tracks + 1], "out_src" [R], "out_cls" [n_tracks] int32 and
+        "rows14" [R, 14] float64 (None unless want_rows14), of which the first n_out_total + 1, R_out, n_out_total and R_out entries
+        are written, and "head" [2 n_scene + 2] int32 = n_out per scene, status per scene, n_out_total, R_out -- ONE small copy
+        tells a caller everything it needs to slice the rest.  Nothing is copied back here."""
+        dev = self.device
+        ao, d_aoff = self._offsets_dev(a_off, torch.int32)
+        ro, d_roff = self._offsets_dev(row_offsets, torch.int32)
+        n_scene, n_tracks, n_rows = len(ao) - 1, int(ao[-1]), int(ro[-1])
+        if len(ro) != n_tracks + 1:
+            raise ValueError(f"merge_assemble: {len(ro) - 1} row ranges for {n_tracks} tracks")
+        if len(img_names_list) != n_scene:
+            raise ValueError("merge_assemble: one list of frame ids per scene")
+        d_rows = self._as_dev(rows, torch.float64)
+        if d_rows.dim() != 2 or d_rows.shape[1] != 14 or d_rows.shape[0] != n_rows:
+            raise ValueError(f"merge_assemble: rows must be [{n_rows}, 14], got {tuple(d_rows.shape)}")
+        tables = [frame_tables(names) for names in img_names_list]
+        io = np.zeros(n_scene + 1, np.int64)
+        io[1:] = np.cumsum([len(t[0]) for t in tables])
+        ids = np.concatenate([t[0] for t in tables]) if tables else np.zeros(0, np.int64)
+        order = np.concatenate([t[1] for t in tables]) if tables else np.zeros(0, np.int32)
+        d_ioff = torch.from_numpy(io.astype(np.int32)).to(dev)
+        d_ids = torch.from_numpy(np.ascontiguousarray(ids, np.int64)).to(dev) if len(ids) else torch.zeros(1, device=dev, dtype=torch.int64)
+        d_ord = torch.from_numpy(np.ascontiguousarray(order, np.int32)).to(dev) if len(ids) else torch.zeros(1, device=dev, dtype=torch.int32)
+        max_cand = int(max((ro[ao[s + 1]] - ro[ao[s]] for s in range(n_scene)), default=0))
+        scratch = torch.empty(n_rows + 4 * n_tracks + 4, device=dev, dtype=torch.int32)
+        out_off = torch.empty(n_tracks + 1, device=dev, dtype=torch.int32)
+        out_src = torch.empty(max(n_rows, 1), device=dev, dtype=torch.int32)
+        out_cls = torch.empty(max(n_tracks, 1), device=dev, dtype=torch.int32)
+        rows14 = torch.empty(max(n_rows, 1), 14, device=dev, dtype=torch.float64) if want_rows14 else None
+        head = torch.zeros(2 * n_scene + 2, device=dev, dtype=torch.int32)
+        if not d_rows.shape[0]:
+            d_rows = torch.zeros(1, 14, device=dev, dtype=torch.float64)
+        labels = clusters["labels"] if clusters["labels"].shape[0] else torch.zeros(1, device=dev, dtype=torch.int32)
+        with torch.cuda.device(dev), self._lock:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_merge_entry("odam_merge_assemble")(
+                self._h, n_scene, _lib.ptr(d_aoff), n_tracks, _lib.ptr(labels), _lib.ptr(clusters["n_cluster"]),
+                _lib.ptr(clusters["status"]), _lib.ptr(d_roff), _lib.ptr(d_rows), n_rows, max_cand, _lib.ptr(d_ioff), _lib.ptr(d_ids),
+                _lib.ptr(d_ord), int(io[-1]), _lib.ptr(scratch), _lib.ptr(out_off), _lib.ptr(out_src), _lib.ptr(out_cls),
+                _lib.ptr(rows14), _lib.ptr(head[:n_scene]), _lib.ptr(head[n_scene:2 * n_scene]), _lib.ptr(head[2 * n_scene:]),
+                ctypes.c_void_p(stream)), "odam_merge_assemble")
+        return {"out_off": out_off, "out_src": out_src[:n_rows], "out_cls": out_cls[:n_tracks],
+                "rows14": None if rows14 is None else rows14[:n_rows], "head": head}
 
     def last_launch(self):
         """shape of the newest fit launch (odam_sq_last_launch): grid, threads per workgroup, workgroups per object, longest-first flag"""
