@@ -220,7 +220,15 @@ int odam_op_bottleneck_f32(const float* x, const float* w2, const float* s2, con
  *   f32.ring.m4.256x64 f32.ring.m4.256x128 f32.ring.m4.256x256 f32.ring.m4.512x64 f32.ring.m4.512x64.pool
  *   f32.fused.m3.l1 f32.fused.m3.chain64 f32.fused.m3.chain128 f32.fused.m3.l2 f32.fused.m4.l1 f32.fused.m4.chain64
  *   f32.fused.m4.chain128 f32.fused.m4.l2
- *   FP32-TOKENS-END */
+ *   FP32-TOKENS-END
+ * The bf16 tokens, all of them (tests/test_conv_bf16_gpu.py covers each):
+ *   BF16-TOKENS-BEGIN
+ *   bf16.small.128x64.w4 bf16.small.128x64.w4.ut bf16.small.128x64.w8 bf16.small.128x64.w8.ut bf16.small.64x64.w4
+ *   bf16.small.64x64.w4.ut bf16.small.64x64.w4.ut.s4 bf16.small.128x128.w4 bf16.small.128x128.w4.ut bf16.small.128x128.w8
+ *   bf16.small.128x128.w8.ut
+ *   bf16.ring.256x64 bf16.ring.256x128 bf16.ring.256x256 bf16.ring.512x64 bf16.ring.512x64.pool
+ *   bf16.fused.p64 bf16.fused.p64.chain64 bf16.fused.p64.chain128 bf16.fused.p128 bf16.fused.p128.chain128 bf16.fused.p256
+ *   BF16-TOKENS-END */
 long long odam_op_conv_paths(char* buf, int n, int reset);
 /* which layers the bf16-native 256-row schedule of the contraction kernel takes: 0 none, 1 those large enough to fill
  * the device (default), 2 every eligible layer (parity tests on small shapes).  Process-wide; also ODAM_CG_BIG. */
