@@ -597,7 +597,8 @@ class Detector:
 
 def build(args):
     """src/models/detr.py:530-573 `build(cfg)` -> (model, criterion, postprocessors); inference only, so the
-    training-time criterion / postprocessors are None.  Reads the same config keys."""
+    training-time criterion / postprocessors are None.  Reads the same config keys.  The second and third values stay None
+    (existing behaviour); the reference's criterion on the device is built from the same config by odam_amd.criterion.build."""
     g = (lambda k, d: args.get(k, d)) if isinstance(args, dict) else (lambda k, d: getattr(args, k, d))
     ds = g("dataset_file", "scan_net")
     num_classes = 18 if ds == "scan_net" else (91 if ds == "coco" else 20)
