@@ -25,6 +25,7 @@
 #include "detr_kernels.h"
 #include "odam_config.h"
 #include "odam_err.h"
+#include "wave_ops.h"
 
 using namespace odam_assoc_internal;      // launch_sinkhorn, PG_GROUPS, PG_BAR_WORDS
 using odam_cg::ConvGemmArgs;
@@ -221,17 +222,6 @@ __device__ void stage_gemm(const float* X, int lda, const float* W, const float*
     }
 }
 
-__device__ __forceinline__ float wave_max64(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // softmax(Q K^T / 8) V per (query row, head) for the queries [r0, r0 + nR), head dimension 64 (associator.py:75-82); one wavefront
 // per item (wave_x, then every n_waves-th): lane j scores key j, lane d accumulates output channel d, 64 source rows at a time (online
 // softmax across chunks); the key rows and the value columns of a chunk are all in flight together.  Keys and values of every row
@@ -265,10 +255,10 @@ __device__ void stage_attn(const float* kv, int T, int cross, float* att, float*
                 acc += qq[d].x * kk[d].x; acc += qq[d].y * kk[d].y; acc += qq[d].z * kk[d].z; acc += qq[d].w * kk[d].w;
             }
             const float sdot = j < nsrc ? acc * 0.125f : -INFINITY;
-            const float mx = fmaxf(run_max, wave_max64(sdot));
+            const float mx = fmaxf(run_max, wave_reduce(sdot, [](float a, float b) { return fmaxf(a, b); }));
             const float p = j < nsrc ? expf(sdot - mx) : 0.0f;
             const float corr = expf(run_max - mx);            // 0 on the first chunk (run_max = -inf)
-            run_sum = run_sum * corr + wave_sum64(p);
+            run_sum = run_sum * corr + wave_sum(p);
             run_max = mx;
             sc[lane] = p;
             __builtin_amdgcn_wave_barrier();

@@ -20,6 +20,7 @@
 #include "../../include/odam_eval.h"
 #include "box_iou_core.h"
 #include "odam_err.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(64) void box3d_match_kernel(MatchArgs M) {
                 }
             }
         }
-        for (int off = 32; off >= 1; off >>= 1) mine = mine + __shfl_xor(mine, off, 64);
+        mine = wave_sum(mine);
         if (lane == 0) {
             M.out_claimed[a0 + p] = mine;
             if (valid) s_cnt[2 * MAX_CLASS + cp] += mine;

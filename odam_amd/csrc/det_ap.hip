@@ -30,6 +30,7 @@
 #include "../../include/odam_eval.h"
 #include "det_ap_core.h"
 #include "odam_err.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -88,11 +89,7 @@ __device__ __forceinline__ int image_of(const ApArgs& K, const int* off, int idx
         const int img = idx / ROW_SLOTS, cnt = off[img];
         return (cnt >= 0 && cnt <= ROW_SLOTS && idx - img * ROW_SLOTS < cnt) ? img : -1;
     }
-    int lo = 0, hi = K.n_image;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= idx) lo = mid; else hi = mid;
-    }
+    const int lo = last_le(off, K.n_image, idx);
     const int a = off[lo], b = off[lo + 1];
     return (a >= 0 && a <= idx && idx < b && b <= n_total) ? lo : -1;
 }

@@ -26,6 +26,7 @@
 #include "dq_core.h"
 #include "dq_ctx.h"
 #include "odam_err.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -46,11 +47,6 @@ struct DqArgs {
     float* traj;
     int* status;            // [n_obj][2]: code, first step
 };
-
-__device__ inline float wave_sum(float x) {
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-    return x;
-}
 
 // NV = 1, 2: a lane keeps its (at most NV) views in registers for the whole fit; NV == 0: it reads them every step (four views per
 // lane in registers need more than the 256 registers of an eight-wave workgroup and spill).  Same arithmetic in every form.

@@ -33,6 +33,7 @@
 #include "../../include/odam_sq.h"
 #include "dq_ctx.h"
 #include "odam_err.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -53,24 +54,6 @@ struct SvdArgs {
     double* out_eig;
     int* status;
 };
-
-__device__ inline double wave_sum(double x) {
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-    return x;
-}
-
-__device__ inline int wave_sum(int x) {
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-    return x;
-}
-
-// LDS traffic between the lanes of ONE wavefront: the wave runs in lockstep and its LDS operations complete in order; this keeps
-// the compiler from moving an access across the point
-__device__ inline void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the rotation that annihilates a_pq: tangent, cosine, sine (Rutishauser's form; theta = +-Inf gives t = 0)
 __device__ inline void jacobi_cs(double app, double aqq, double apq, double& t, double& c, double& s) {

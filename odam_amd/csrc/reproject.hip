@@ -13,7 +13,7 @@
 //   reproject_score_kernel  per view the four residuals |ext - box| (mask, NaN -> 0, as :423-428) and the IoU of the detected box with
 //                           the predicted box clipped to the image; per object their sums.  One wavefront per object.
 //
-// Summation order of the score kernel (that of dq_fit.hip; tests/dq_ref.wave_sums): lane l adds the views l, l + 64, ... in
+// Summation order of the score kernel (wave_sum of wave_ops.h; tests/dq_ref.wave_sums): lane l adds the views l, l + 64, ... in
 // ascending order to a partial that starts at +0; the 64 partials go through the butterfly partner = lane XOR 32, 16, 8, 4, 2, 1.
 // The smallest IoU is merged as the pair (value, view) -- the smaller value, of equal values the smaller view -- so worst_view is
 // the first view with the smallest IoU whatever the order.
@@ -30,6 +30,7 @@
 #include "dq_ctx.h"
 #include "odam_err.h"
 #include "reproject_core.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -79,13 +80,11 @@ __global__ __launch_bounds__(64 * SQ_WAVES) void reproject_sq_kernel(SqArgs A) {
                 cnt++;
             }
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            e0 = min_nan(e0, __shfl_xor(e0, off, 64));
-            e1 = max_nan(e1, __shfl_xor(e1, off, 64));
-            e2 = min_nan(e2, __shfl_xor(e2, off, 64));
-            e3 = max_nan(e3, __shfl_xor(e3, off, 64));
-            cnt = cnt + __shfl_xor(cnt, off, 64);
-        }
+        e0 = wave_reduce(e0, min_nan<float>);
+        e1 = wave_reduce(e1, max_nan<float>);
+        e2 = wave_reduce(e2, min_nan<float>);
+        e3 = wave_reduce(e3, max_nan<float>);
+        cnt = wave_sum(cnt);
         if (lane < 4) {
             const float e = (lane == 0) ? e0 : (lane == 1) ? e1 : (lane == 2) ? e2 : e3;
             A.out_ext[row * 4 + lane] = store_ext(e);
@@ -176,18 +175,8 @@ __global__ __launch_bounds__(512) void reproject_score_kernel(ScoreArgs<T> A) {
         if (iou < mn) { mn = iou; mi = v; }
         nb += bad ? 1 : 0;
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        s0 = s0 + __shfl_xor(s0, off, 64);
-        s1 = s1 + __shfl_xor(s1, off, 64);
-        s2 = s2 + __shfl_xor(s2, off, 64);
-        s3 = s3 + __shfl_xor(s3, off, 64);
-        si = si + __shfl_xor(si, off, 64);
-        ne = ne + __shfl_xor(ne, off, 64);
-        nb = nb + __shfl_xor(nb, off, 64);
-        const T omn = __shfl_xor(mn, off, 64);
-        const int omi = __shfl_xor(mi, off, 64);
-        if (omn < mn || (omn == mn && omi < mi)) { mn = omn; mi = omi; }
-    }
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3); si = wave_sum(si); ne = wave_sum(ne); nb = wave_sum(nb);
+    wave_reduce_pair(mn, mi, [](T omn, int omi, T mn, int mi) { return omn < mn || (omn == mn && omi < mi); });
     const T Ff = (T)F;
     const T loss = ((s0 / Ff + s1 / Ff) + s2 / Ff) + s3 / Ff;
     const T mean_abs = (ne > 0) ? (((s0 + s1) + s2) + s3) / (T)ne : qnan;

@@ -39,6 +39,7 @@
 #include "odam_err.h"
 #include "sq_core.h"
 #include "dq_ctx.h"
+#include "wave_ops.h"
 
 namespace {
 using namespace odam_sq;
@@ -1220,11 +1221,9 @@ __global__ __launch_bounds__(256) void project_extent_kernel(const float* __rest
         const double u = q0 / q2, v = q1 / q2;
         umin = fmin(umin, u); umax = fmax(umax, u); vmin = fmin(vmin, v); vmax = fmax(vmax, v);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        umin = fmin(umin, __shfl_xor(umin, o)); vmin = fmin(vmin, __shfl_xor(vmin, o));
-        umax = fmax(umax, __shfl_xor(umax, o)); vmax = fmax(vmax, __shfl_xor(vmax, o));
-    }
+    const auto lo = [](double a, double b) { return fmin(a, b); };
+    const auto hi = [](double a, double b) { return fmax(a, b); };
+    umin = wave_reduce(umin, lo); vmin = wave_reduce(vmin, lo); umax = wave_reduce(umax, hi); vmax = wave_reduce(vmax, hi);
     if (lane == 0) { red[wave][0] = umin; red[wave][1] = vmin; red[wave][2] = umax; red[wave][3] = vmax; }
     __syncthreads();
     if (tid < 4) {

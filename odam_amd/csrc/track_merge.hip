@@ -12,7 +12,7 @@
 // definition and run on one lane (O(n log n) LDS operations at n <= 1024).
 //
 // Assembly: one workgroup per (scene, label).  The members are ranked by (rows descending, track ascending); their rows, enumerated in
-// that order, become the keys (image << 32 | candidate) of the rows whose frame id names an image; after a bitonic sort in LDS the
+// that order, become the keys (image << 32 | candidate, view_keys.h) of the rows whose frame id names an image; after the LDS sort the
 // first key of every image run is the row the host path would keep.  A scan over all clusters gives the dense offsets, a gather
 // writes the rows.  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -24,21 +24,18 @@
 #include "../../include/odam_merge.h"
 #include "odam_err.h"
 #include "track_merge_core.h"
+#include "view_keys.h"
+#include "wave_ops.h"
 
 namespace {
 
 constexpr int MAXN = ODAM_MERGE_MAX_TRACKS;
 constexpr int MAX_WAVES = 16;
 constexpr int N_CLASS = 64;
-constexpr unsigned long long NO_VIEW = ~0ull;
 
 // the scene that owns track (or cluster slot) g, or -1 when the offsets do not say so consistently
 __device__ inline int scene_of(const int* a_off, int n_scene, int n_tracks, int g) {
-    int lo = 0, hi = n_scene;      // first s with a_off[s + 1] > g
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a_off[mid + 1] <= g) lo = mid + 1; else hi = mid;
-    }
+    const int lo = first_owner(a_off, n_scene, g);
     if (lo >= n_scene) return -1;
     const int t0 = a_off[lo], t1 = a_off[lo + 1];
     if (t0 < 0 || t1 > n_tracks || g < t0 || g >= t1 || t1 - t0 > MAXN) return -1;
@@ -129,11 +126,7 @@ __global__ __launch_bounds__(512) void merge_cluster_kernel(ClusterArgs A) {
             const double v = row[i];
             if (tm_better(v, i, bv, bi)) { bv = v; bi = i; }
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double ov = __shfl_xor(bv, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (tm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
+        wave_reduce_pair(bv, bi, [](double ov, int oi, double v, int i) { return tm_better(ov, oi, v, i); });
         if (lane == 0) { s_wv[wave] = bv; s_wi[wave] = bi; }
         __syncthreads();
         if (tid == 0) {
@@ -271,21 +264,6 @@ struct AsmArgs {
     int *out_n_out, *out_status, *out_total;
 };
 
-__device__ inline bool first_of_image(const unsigned long long* keys, int j) {
-    const unsigned long long k = keys[j];
-    return k != NO_VIEW && (j == 0 || (unsigned)(keys[j - 1] >> 32) != (unsigned)(k >> 32));
-}
-
-// the ranked member that owns candidate j: the last q with base[q] <= j
-__device__ inline int member_of(const int* base, int M, int j) {
-    int lo = 0, hi = M;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (base[mid] <= j) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     __shared__ int s_mem[MAXN], s_len[MAXN], s_ord[MAXN], s_r0[MAXN], s_base[MAXN + 1];
@@ -318,16 +296,9 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
     for (int base = 0; base < n; base += T) {
         const int t = base + tid;
         const bool in = t < n && A.labels[t0 + t] == c;
-        const unsigned long long b = __ballot(in);
-        const int before = __popcll(b & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wcnt[wave] = __popcll(b);
-        __syncthreads();
-        int at = M, tot = 0;
-        for (int w = 0; w < n_waves; w++) {
-            if (w < wave) at += s_wcnt[w];
-            tot += s_wcnt[w];
-        }
-        if (in) s_mem[at + before] = t;
+        int tot;
+        const int before = wg_exclusive_scan(in ? 1 : 0, tot, s_wcnt, lane, wave, n_waves);
+        if (in) s_mem[M + before] = t;
         M += tot;
         __syncthreads();
     }
@@ -376,9 +347,9 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
     const long long* ids = A.img_ids + i0;
     const int* order = A.img_order + i0;
     for (int j = tid; j < n2; j += T) {
-        unsigned long long key = NO_VIEW;
+        unsigned long long key = VIEW_NONE;
         if (j < C) {
-            const int q = member_of(s_base, M, j);
+            const int q = last_le(s_base, M, j);      // the ranked member that owns candidate j
             const int mq = s_ord[q];
             const double* row = A.rows + ((size_t)s_r0[mq] + (size_t)(j - s_base[q])) * 14;
             const double f = row[0];
@@ -389,7 +360,7 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
             }
             if (lo < n_img && (double)ids[lo] == f) {
                 const int img = order[lo];
-                if (img >= 0 && img < n_img) key = ((unsigned long long)(unsigned)img << 32) | (unsigned)j;
+                if (img >= 0 && img < n_img) key = view_key(img, j);
             }
             const double cl = row[1];
             if (cl >= 0.0 && cl <= (double)(N_CLASS - 1) && cl == floor(cl)) atomicAdd(&s_hist[(int)cl], 1);
@@ -399,18 +370,7 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
     }
     __syncthreads();
 
-    // bitonic sort, ascending
-    for (int kk = 2; kk <= n2; kk <<= 1)
-        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-            for (int idx = tid; idx < (n2 >> 1); idx += T) {
-                const int a = ((idx & ~(jj - 1)) << 1) | (idx & (jj - 1));
-                const int b = a | jj;
-                const unsigned long long ka = keys[a], kb = keys[b];
-                const bool up = (a & kk) == 0;
-                if ((ka > kb) == up) { keys[a] = kb; keys[b] = ka; }
-            }
-            __syncthreads();
-        }
+    lds_bitonic_sort(keys, n2, tid, T);
 
     // every thread owns a run of L sorted entries; winners in front of it = where its own winners go
     const int L = n2 > T ? n2 / T : 1;
@@ -420,27 +380,17 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
     for (int j = j0; j < j1; j++) {
         if (first_of_image(keys, j)) { cnt++; continue; }
         const unsigned long long key = keys[j];
-        if (key == NO_VIEW) continue;
+        if (key == VIEW_NONE) continue;
         // same image as its left neighbour: two members saw the image, or one member holds the frame id twice
-        const int qa = member_of(s_base, M, (int)(keys[j - 1] & 0xffffffffu)), qb = member_of(s_base, M, (int)(key & 0xffffffffu));
+        const int qa = last_le(s_base, M, view_index(keys[j - 1])), qb = last_le(s_base, M, view_index(key));
         if (qa == qb) atomicMax(&s_bad, ODAM_MERGE_REPEATED_FRAME);
     }
-    int incl = cnt;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) s_wcnt[wave] = incl;
-    __syncthreads();
-    int p = incl - cnt, total = 0;
-    for (int w = 0; w < n_waves; w++) {
-        if (w < wave) p += s_wcnt[w];
-        total += s_wcnt[w];
-    }
+    int total;
+    int p = wg_exclusive_scan(cnt, total, s_wcnt, lane, wave, n_waves);
     for (int j = j0; j < j1; j++) {
         if (!first_of_image(keys, j)) continue;
-        const int cand = (int)(keys[j] & 0xffffffffu);
-        const int q = member_of(s_base, M, cand);
+        const int cand = view_index(keys[j]);
+        const int q = last_le(s_base, M, cand);
         A.sel_rank[s_r0[s_ord[q]] + (cand - s_base[q])] = p;
         p++;
     }
@@ -457,7 +407,7 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(AsmArgs A) {
 
 // dense offsets over all cluster slots: ONE workgroup
 __global__ __launch_bounds__(1024) void merge_scan_kernel(AsmArgs A) {
-    __shared__ int s_wk[MAX_WAVES], s_wr[MAX_WAVES];
+    __shared__ int s_w[2 * MAX_WAVES];      // kept clusters, rows
     const int tid = threadIdx.x, T = blockDim.x;
     const int lane = tid & 63, wave = tid >> 6, n_waves = T >> 6;
     const int G = A.n_tracks;
@@ -471,24 +421,15 @@ __global__ __launch_bounds__(1024) void merge_scan_kernel(AsmArgs A) {
             if (cnt < 0 || cnt > A.n_rows) cnt = 0;
         }
         const int keep = cnt > 0 ? 1 : 0;
-        int ik = keep, ir = cnt;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int uk = __shfl_up(ik, off, 64), ur = __shfl_up(ir, off, 64);
-            if (lane >= off) { ik += uk; ir += ur; }
-        }
-        if (lane == 63) { s_wk[wave] = ik; s_wr[wave] = ir; }
-        __syncthreads();
-        int ek = carry_k + ik - keep, er = carry_r + ir - cnt, tk = 0, tr = 0;
-        for (int w = 0; w < n_waves; w++) {
-            if (w < wave) { ek += s_wk[w]; er += s_wr[w]; }
-            tk += s_wk[w]; tr += s_wr[w];
-        }
+        int excl[2] = {keep, cnt}, tot[2];
+        wg_exclusive_scan(excl, tot, s_w, lane, wave, n_waves);
+        const int ek = carry_k + excl[0], er = carry_r + excl[1];
         if (g < G) {
             A.dense_excl[g] = ek;
             A.slot_base[g] = er <= A.n_rows - cnt ? er : -1;      // (rows are chosen once each: the sum cannot pass n_rows)
             if (keep) { A.out_off[ek] = er; A.out_cls[ek] = A.slot_cls[g]; }
         }
-        carry_k += tk; carry_r += tr;
+        carry_k += tot[0]; carry_r += tot[1];
         __syncthreads();
     }
     if (tid == 0) {
@@ -514,11 +455,7 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(AsmArgs A) {
     if (r >= A.n_rows) return;
     const int p = A.sel_rank[r];
     if (p < 0) return;
-    int lo = 0, hi = A.n_tracks;      // the track that owns row r: the first t with row_off[t + 1] > r
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (A.row_off[mid + 1] <= r) lo = mid + 1; else hi = mid;
-    }
+    const int lo = first_owner(A.row_off, A.n_tracks, r);      // the track that owns row r
     if (lo >= A.n_tracks || A.row_off[lo] > r) return;
     const int s = scene_of(A.a_off, A.n_scene, A.n_tracks, lo);
     if (s < 0 || A.cluster_status[s] != 0 || A.out_status[s] != 0) return;

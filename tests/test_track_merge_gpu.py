@@ -187,6 +187,29 @@ def test_assembly_statuses_are_reported_per_scene(fitter):
     check_assemble(got, rows, ref)
 
 
+def test_assembly_scan_carries_past_1024_cluster_slots(fitter):
+    """three scenes of 500 + 400 + 200 tracks, every track its own cluster: 1100 cluster slots in one call, so the one-workgroup scan
+    over the slots takes a second trip that starts from the first trip's carry; tracks of one or two rows, every seventh on frames
+    that name no image (a slot that keeps nothing: the two scanned counts differ)"""
+    scenes = []
+    for s, n in enumerate((500, 400, 200)):
+        rs = np.random.RandomState(40 + s)
+        img_names = [int(v) for v in rs.permutation(np.arange(12) * 3 + 7)]
+        tracks = []
+        for t in range(n):
+            k = int(rs.randint(1, 3))
+            tr = rs.uniform(-1, 1, (k, 14))
+            tr[:, 0] = rs.choice(img_names, k, replace=False) + (1 if t % 7 == 3 else 0)      # + 1: between the images' ids
+            tr[:, 1] = rs.randint(0, 8)
+            tracks.append(tr)
+        scenes.append((tracks, np.arange(n, dtype=np.int32), n, img_names))
+    ref = R.assemble(scenes)
+    assert ref["status"].tolist() == [0, 0, 0] and ref["n_out"].tolist() == [500 - 71, 400 - 57, 200 - 29]
+    assert sum(len(s[0]) for s in scenes) > 1024
+    got, rows = run_assemble(fitter, scenes)
+    check_assemble(got, rows, ref)
+
+
 # ---- 3. end to end ---------------------------------------------------------------------------------------------------------------------
 def test_merge_process_on_device_returns_the_reference_tracks(fitter, golden):
     from odam_amd import merge
