@@ -206,162 +206,51 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ Q,
 }
 
 // =================================================================================================
-// Fused attention on the bf16 matrix instruction (bf16 mode, BASELINE config 4), d_head = 32.
-// Same dataflow as above with v_mfma_f32_32x32x16_bf16: per 64-key tile 4 MFMAs give S^T = K . Q^T (two 32-key blocks x
-// two 16-channel k-steps) and 4 more O^T += V^T . P^T -- 8 x 32 cycles instead of 64 x 64.  P stays in registers: the
-// S^T accumulator (query on the lane, key in the register) converted pairwise to bf16 IS the B operand of the PV
-// product; its k order inside a 16-key step is 16 s + 8 (j >> 2) + 4 half + (j & 3), so the A operand (V^T) is read
-// from an LDS image [channel][key] as two 4-key groups per step.  Softmax in fp32 with exp2 (scale * log2 e folded in).
-// LDS: K tile [64 keys][64 B] with the 16-byte chunk c of key r at c ^ ((r >> 2) & 3) (conflict-free ds_read_b128, as
-// in conv_gemm's bf16 kernel); V tile [64 keys][64 B] row-major, read transposed by ds_read_b64_tr_b16 (see the kernel).
+// Attention on v_mfma_f32_32x32x16_bf16: what attention_bf16_kernel<D> and attention_x3_kernel<D> below share.  D = head dim, 32
+// or 64; workgroup, query ownership and the online softmax's shape are attention_kernel's.
+//
+// LDS image of a key tile: one row of 2 D bytes per key, NC = D / 8 chunks of 16 bytes (8 bf16 channels) per row.
+//   K: chunk c of key r sits at c ^ ((r >> 2) & 3) at D = 32 (64-byte rows, as in conv_gemm's bf16 kernel) and at
+//      c ^ ((r >> 1) & 7) at D = 64 (128-byte rows, two keys per 256-byte bank row): the ds_read_b128 lane groups of the QK^T
+//      step are conflict-free at both.
+//   V: row-major as it comes from HBM (one 16-byte store per chunk) and read through ds_read_b64_tr_b16, the hardware
+//      transpose: a 16-lane group reads a block of 4 keys x 16 channels and lane i receives channel i of the four keys --
+//      the PV product's A operand (V^T: channel on the lane, four consecutive keys in the register pair).  Lane 4 q + p of
+//      16-lane group g supplies the address of key row q, channels 4 p .. 4 p + 3 of the group's channel block (g & 1); the
+//      group's half (g >> 1) selects keys 4 half .. of an 8-key step, as the P operand's k order wants them.  At D = 32 the
+//      32 lanes of a half read 4 keys x 64 bytes = 256 contiguous bytes: conflict-free without a swizzle.  At D = 64 a row keeps
+//      its two 64-byte halves swapped where bit 1 of the key is set (the four keys of a transposed read then cover all 64
+//      banks), so the half holding output tile o is o ^ (bit 1 of the lane's key row q).
 // =================================================================================================
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef short tr4_t __attribute__((ext_vector_type(4)));
+typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
 
-__global__ __launch_bounds__(256) void attention_bf16_kernel(const bf16_t* __restrict__ Q, int ldq,
-                                                             const bf16_t* __restrict__ K, int ldk,
-                                                             const bf16_t* __restrict__ V, int ldv,
-                                                             bf16_t* __restrict__ O, int ldo, int Lq, int Lk, float c_log2,
-                                                             const unsigned char* __restrict__ key_mask) {
-    constexpr int KT = 64, D = 32;
-    __shared__ __align__(16) uint4 Ks[2][KT * 4];
-    // V stays row-major in LDS ([key][32 channels], 64-byte rows, as it comes from HBM: one 16-byte store per thread) and reaches the PV
-    // product's A operand (V^T: channel on the lane, four consecutive keys in the register pair) through ds_read_b64_tr_b16 -- the hardware
-    // transpose: a 16-lane group reads a block of 4 keys x 16 channels and lane i receives channel i of the four keys.  (Round 6; until
-    // then every thread wrote its 8 values into a transposed image with 8 two-byte stores per tile.  Same values in the same operand
-    // lanes: bit-identical.)  The 32 lanes of a half read 4 keys x 64 bytes = 256 contiguous bytes: conflict-free without a swizzle.
-    __shared__ __align__(16) uint4 Vs[2][KT * 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, col = lane & 31;
-    const int h = blockIdx.y, b = blockIdx.z;
-    const int q0 = blockIdx.x * 128 + wave * 32;
-    const bf16_t* Qb = Q + (size_t)b * Lq * ldq + h * D;
-    const bf16_t* Kb = K + (size_t)b * Lk * ldk + h * D;
-    const bf16_t* Vb = V + (size_t)b * Lk * ldv + h * D;
-
-    uint4 qf[2];     // B operand of S^T = K . Q^T: lane (query col, half) holds Q[q][16 s + 8 half .. + 7]
-    {
-        const int q = q0 + col;
-#pragma unroll
-        for (int st = 0; st < 2; st++)
-            qf[st] = (q < Lq) ? *reinterpret_cast<const uint4*>(Qb + (size_t)q * ldq + 16 * st + 8 * half) : uint4{0u, 0u, 0u, 0u};
-    }
-    const int lk = tid >> 2, lc = tid & 3;          // loader: key row of the tile, 8-channel chunk
-    auto load_kv = [&](int kt, uint4& kr, uint4& vr) {
-        const int key = kt * KT + lk;
-        if (key < Lk) {
-            kr = *reinterpret_cast<const uint4*>(Kb + (size_t)key * ldk + lc * 8);
-            vr = *reinterpret_cast<const uint4*>(Vb + (size_t)key * ldv + lc * 8);
-        } else {
-            kr = uint4{0u, 0u, 0u, 0u}; vr = uint4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto store_kv = [&](int buf, const uint4& kr, const uint4& vr) {
-        Ks[buf][lk * 4 + (lc ^ ((lk >> 2) & 3))] = kr;
-        Vs[buf][lk * 4 + lc] = vr;
-    };
-    // transposed read of V: lane 4 q + p of 16-lane group g supplies the address of key row q, channels 4 p .. 4 p + 3 of the group's
-    // channel block (g & 1); the group's half (g >> 1) selects keys 4 half .. of an 8-key step, as the P operand's k order wants them
-    typedef short tr4_t __attribute__((ext_vector_type(4)));
-    const int tr_off = (((lane >> 5) * 4 + ((lane & 15) >> 2)) * 64) + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;      // bytes inside a tile image
-
-    floatx16 oacc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) oacc[r] = 0.0f;
-    float m_run = -1e30f, l_run = 0.0f;
-    const int ntiles = (Lk + KT - 1) / KT;
-    uint4 kr, vr;
-    load_kv(0, kr, vr);
-    store_kv(0, kr, vr);
-    __syncthreads();
-    for (int kt = 0; kt < ntiles; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < ntiles) load_kv(kt + 1, kr, vr);
-        floatx16 s[2];
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) s[jh][r] = 0.0f;
-            const int key = jh * 32 + col;
-#pragma unroll
-            for (int st = 0; st < 2; st++) {
-                const uint4 kf = Ks[cur][key * 4 + ((2 * st + half) ^ ((key >> 2) & 3))];
-                s[jh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, kf), __builtin_bit_cast(bf16x8_t, qf[st]),
-                                                                s[jh], 0, 0, 0);
-            }
-        }
-        const int kbase = kt * KT;
-        if (kbase + KT > Lk || key_mask) {
-            const unsigned char* mk = key_mask ? key_mask + (size_t)b * Lk + kbase : nullptr;
-#pragma unroll
-            for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int k = jh * 32 + acc_row(r, half);
-                    if (kbase + k >= Lk || (mk && mk[k])) s[jh][r] = -1e30f;
-                }
-        }
-        float mx = s[0][0];
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) mx = fmaxf(mx, s[jh][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c_log2);
-        const float mc = m_new * c_log2;
-        float psum = 0.0f;
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                s[jh][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[jh][r], c_log2, -mc));
-                psum += s[jh][r];
-            }
-        psum += __shfl_xor(psum, 32);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; r++) oacc[r] *= alpha;
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-            for (int st = 0; st < 2; st++) {
-                unsigned pw[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    pw[e] = pack_bf16x2(s[jh][8 * st + 2 * e], s[jh][8 * st + 2 * e + 1]);
-                typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
-                const char* vb = reinterpret_cast<const char*>(&Vs[cur][0]) + (jh * 32 + 16 * st) * 64 + tr_off;
-                const tr4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb));               // keys 4 half .. + 3 of the step
-                const tr4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 64));      // keys 8 + 4 half .. + 3
-                const uint2 lo = __builtin_bit_cast(uint2, lo4), hi = __builtin_bit_cast(uint2, hi4);
-                const uint4 vf = uint4{lo.x, lo.y, hi.x, hi.y};
-                oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vf),
-                                                               __builtin_bit_cast(bf16x8_t, uint4{pw[0], pw[1], pw[2], pw[3]}), oacc, 0, 0, 0);
-            }
-        if (kt + 1 < ntiles) store_kv(cur ^ 1, kr, vr);
-        __syncthreads();
-    }
-    const int q = q0 + col;
-    if (q < Lq) {
-        const float inv = 1.0f / l_run;
-        bf16_t* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
-#pragma unroll
-        for (int g = 0; g < 4; g++)
-            st4(Ob + 8 * g + 4 * half, float4{oacc[4 * g + 0] * inv, oacc[4 * g + 1] * inv, oacc[4 * g + 2] * inv, oacc[4 * g + 3] * inv});
-    }
+template <int D> __device__ __forceinline__ int att_kswz(int r, int c) {      // index of 16-byte chunk c of key r in a K tile
+    if constexpr (D == 32) return r * 4 + (c ^ ((r >> 2) & 3));
+    else return r * 8 + (c ^ ((r >> 1) & 7));
 }
-
-// =================================================================================================
-// Fused attention for fp32 operands on the bf16 matrix instruction, d_head = 32: the dataflow of attention_bf16_kernel
-// with every product taken through the exact three-way bf16 split of conv_gemm.hip (a = hi + mid + lo by truncation, six
-// bf16 x bf16 products per fp32 product, fp32 accumulate; max error vs float64 0.8-1.4e-7 of sum |a b|, the fp32 matrix
-// instruction's own chain 1.1-1.9e-7).  K and V tiles are split once when they are staged (three bf16 planes each in
-// LDS, K key-major with the swizzle of the bf16 kernel, V transposed), the pre-scaled query fragment is split once per
-// workgroup, the probabilities -- fp32 in the S^T accumulators -- are split in registers and are the B operand of the PV
-// product as they stand.  Per 64-key tile and wave 48 matrix instructions of 32 cycles against 64 of 64 on
-// v_mfma_f32_32x32x2_f32.  Softmax as in the fp32 kernel (q pre-scaled, __expf).
-// =================================================================================================
+template <int D> __device__ __forceinline__ int att_vswz(int r, int c) {      // the same in a V tile
+    if constexpr (D == 32) return r * 4 + c;
+    else return r * 8 + (c ^ (((r >> 1) & 1) << 2));
+}
+// byte offset inside a V tile of this lane's transposed read for the 32-channel output tile o
+template <int D> __device__ __forceinline__ int att_tr_off(int lane, int o) {
+    const int blk = D == 32 ? 0 : o ^ ((lane >> 3) & 1);
+    return (((lane >> 5) * 4 + ((lane & 15) >> 2)) * 2 * D) + ((blk * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2);
+}
+// V^T fragment of one 16-key step: keys 4 half .. + 3 and 8 + 4 half .. + 3 of the step that starts at vb
+template <int D> __device__ __forceinline__ uint4 att_read_vt(const char* vb) {
+    const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb)));
+    const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 2 * D)));
+    return uint4{lo.x, lo.y, hi.x, hi.y};
+}
+__device__ __forceinline__ void att_mma(floatx16& acc, const uint4& a, const uint4& b) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
+}
+// (The epilogue, eight lines, is written out in both kernels: behind a helper it costs attention_x3_kernel<32> two more s_waitcnt
+// vmcnt(0), one of them in the key loop -- profiles/attention_template.txt.)
+// exact three-way bf16 split of eight fp32 values (a = hi + mid + lo by truncation), as conv_gemm.hip's: one uint4 of bf16 per plane
 __device__ __forceinline__ void att_split8(const float4& c0, const float4& c1, uint4& hi, uint4& mid, uint4& lo) {
     const float v[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
     unsigned uh[8], um[8], ul[8];
@@ -378,189 +267,40 @@ __device__ __forceinline__ void att_split8(const float4& c0, const float4& c1, u
     lo = uint4{pk(ul[0], ul[1]), pk(ul[2], ul[3]), pk(ul[4], ul[5]), pk(ul[6], ul[7])};
 }
 
-__global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restrict__ Q, int ldq,
-                                                           const float* __restrict__ K, int ldk,
-                                                           const float* __restrict__ V, int ldv,
-                                                           float* __restrict__ O, int ldo, int Lq, int Lk, float scale,
-                                                           const unsigned char* __restrict__ key_mask) {
-    constexpr int KT = 64, D = 32;
-    __shared__ __align__(16) uint4 Ks[2][3][KT * 4];
-    __shared__ __align__(16) uint4 Vs[2][3][KT * 4];      // V's three planes row-major, read transposed (ds_read_b64_tr_b16) as in attention_bf16_kernel
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, col = lane & 31;
-    const int h = blockIdx.y, b = blockIdx.z;
-    const int q0 = blockIdx.x * 128 + wave * 32;
-    const float* Qb = Q + (size_t)b * Lq * ldq + h * D;
-    const float* Kb = K + (size_t)b * Lk * ldk + h * D;
-    const float* Vb = V + (size_t)b * Lk * ldv + h * D;
-
-    uint4 qh[2], qm[2], ql[2];     // B operand of S^T = K . Q^T: lane (query col, half) holds Q[q][16 s + 8 half .. + 7], pre-scaled
-    {
-        const int q = q0 + col;
-#pragma unroll
-        for (int st = 0; st < 2; st++) {
-            float4 a = float4{0.f, 0.f, 0.f, 0.f}, c = a;
-            if (q < Lq) {
-                a = ld4(Qb + (size_t)q * ldq + 16 * st + 8 * half);
-                c = ld4(Qb + (size_t)q * ldq + 16 * st + 8 * half + 4);
-            }
-            a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;
-            c.x *= scale; c.y *= scale; c.z *= scale; c.w *= scale;
-            att_split8(a, c, qh[st], qm[st], ql[st]);
-        }
-    }
-    const int lk = tid >> 2, lc = tid & 3;          // loader: key row of the tile, 8-channel chunk
-    auto load_kv = [&](int kt, float4 (&kr)[2], float4 (&vr)[2]) {
-        const int key = kt * KT + lk;
-        if (key < Lk) {
-            kr[0] = ld4(Kb + (size_t)key * ldk + lc * 8); kr[1] = ld4(Kb + (size_t)key * ldk + lc * 8 + 4);
-            vr[0] = ld4(Vb + (size_t)key * ldv + lc * 8); vr[1] = ld4(Vb + (size_t)key * ldv + lc * 8 + 4);
-        } else {
-            kr[0] = kr[1] = vr[0] = vr[1] = float4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto store_kv = [&](int buf, const float4 (&kr)[2], const float4 (&vr)[2]) {
-        uint4 p[3];
-        att_split8(kr[0], kr[1], p[0], p[1], p[2]);
-#pragma unroll
-        for (int pl = 0; pl < 3; pl++) Ks[buf][pl][lk * 4 + (lc ^ ((lk >> 2) & 3))] = p[pl];
-        att_split8(vr[0], vr[1], p[0], p[1], p[2]);
-#pragma unroll
-        for (int pl = 0; pl < 3; pl++) Vs[buf][pl][lk * 4 + lc] = p[pl];
-    };
-    typedef short tr4_t __attribute__((ext_vector_type(4)));
-    typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
-    const int tr_off = (((lane >> 5) * 4 + ((lane & 15) >> 2)) * 64) + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;      // see attention_bf16_kernel
-#define ODAM_MMA(acc, a, bq) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, bq), acc, 0, 0, 0)
-
-    floatx16 oacc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) oacc[r] = 0.0f;
-    float m_run = -1e30f, l_run = 0.0f;
-    const int ntiles = (Lk + KT - 1) / KT;
-    float4 kr[2], vr[2];
-    load_kv(0, kr, vr);
-    store_kv(0, kr, vr);
-    __syncthreads();
-    for (int kt = 0; kt < ntiles; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < ntiles) load_kv(kt + 1, kr, vr);
-        floatx16 s[2];
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) s[jh][r] = 0.0f;
-            const int key = jh * 32 + col;
-#pragma unroll
-            for (int st = 0; st < 2; st++) {
-                const int idx = key * 4 + ((2 * st + half) ^ ((key >> 2) & 3));
-                const uint4 kh = Ks[cur][0][idx], km = Ks[cur][1][idx], kl = Ks[cur][2][idx];
-                ODAM_MMA(s[jh], kl, qh[st]); ODAM_MMA(s[jh], km, qm[st]); ODAM_MMA(s[jh], kh, ql[st]);     // smallest products first
-                ODAM_MMA(s[jh], km, qh[st]); ODAM_MMA(s[jh], kh, qm[st]);
-                ODAM_MMA(s[jh], kh, qh[st]);
-            }
-        }
-        const int kbase = kt * KT;
-        if (kbase + KT > Lk || key_mask) {
-            const unsigned char* mk = key_mask ? key_mask + (size_t)b * Lk + kbase : nullptr;
-#pragma unroll
-            for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int k = jh * 32 + acc_row(r, half);
-                    if (kbase + k >= Lk || (mk && mk[k])) s[jh][r] = -1e30f;
-                }
-        }
-        float mx = s[0][0];
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) mx = fmaxf(mx, s[jh][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = __expf(m_run - m_new);
-        float psum = 0.0f;
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                s[jh][r] = __expf(s[jh][r] - m_new);
-                psum += s[jh][r];
-            }
-        psum += __shfl_xor(psum, 32);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; r++) oacc[r] *= alpha;
-        // O^T += V^T . P^T: the accumulator registers 8 st .. 8 st + 7 of s[jh], split, are the B operand of k-step (jh, st)
-#pragma unroll
-        for (int jh = 0; jh < 2; jh++)
-#pragma unroll
-            for (int st = 0; st < 2; st++) {
-                uint4 ph, pm, pl_;
-                att_split8(float4{s[jh][8 * st + 0], s[jh][8 * st + 1], s[jh][8 * st + 2], s[jh][8 * st + 3]},
-                           float4{s[jh][8 * st + 4], s[jh][8 * st + 5], s[jh][8 * st + 6], s[jh][8 * st + 7]}, ph, pm, pl_);
-                uint4 vf[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; pl++) {
-                    const char* vb = reinterpret_cast<const char*>(&Vs[cur][pl][0]) + (jh * 32 + 16 * st) * 64 + tr_off;
-                    const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb)));
-                    const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 64)));
-                    vf[pl] = uint4{lo.x, lo.y, hi.x, hi.y};
-                }
-                ODAM_MMA(oacc, vf[2], ph); ODAM_MMA(oacc, vf[1], pm); ODAM_MMA(oacc, vf[0], pl_);
-                ODAM_MMA(oacc, vf[1], ph); ODAM_MMA(oacc, vf[0], pm);
-                ODAM_MMA(oacc, vf[0], ph);
-            }
-        if (kt + 1 < ntiles) store_kv(cur ^ 1, kr, vr);
-        __syncthreads();
-    }
-#undef ODAM_MMA
-    const int q = q0 + col;
-    if (q < Lq) {
-        const float inv = 1.0f / l_run;
-        float* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
-#pragma unroll
-        for (int g = 0; g < 4; g++)
-            st4(Ob + 8 * g + 4 * half, float4{oacc[4 * g + 0] * inv, oacc[4 * g + 1] * inv, oacc[4 * g + 2] * inv, oacc[4 * g + 3] * inv});
-    }
-}
-
 // =================================================================================================
-// Head dim 64 (hidden_dim / nheads = 64): attention_bf16_kernel and attention_x3_kernel restated for 64 channels per head.
-// Same dataflow, rounding points and softmax; per key tile 4 k-steps of S^T = K . Q^T instead of 2 and two 32-channel output
-// tiles of O^T.  K / V rows are 128 bytes in LDS: K chunk c of key r sits at c ^ ((r >> 1) & 7) (two keys per 256-byte bank
-// row: the ds_read_b128 lane groups stay conflict-free), and a V row keeps its two 64-byte halves swapped where bit 1 of the key
-// is set (the four keys of a transposed read then cover all 64 banks).  At twice the head width a score tile feeds twice the
-// matrix work per exponential.  The D = 32 kernels above are left as they are.
+// Fused attention on the bf16 matrix instruction (bf16 and mxfp8 modes), head dim D = 32 or 64.
+// The dataflow of attention_kernel with v_mfma_f32_32x32x16_bf16: per 64-key tile 2 NS MFMAs give S^T = K . Q^T (two 32-key
+// blocks x NS = D / 16 k-steps of 16 channels) and 4 NO more O^T += V^T . P^T (NO = D / 32 output tiles of 32 channels) -- at
+// D = 32, 8 x 32 cycles instead of 64 x 64.  P stays in registers: the S^T accumulator (query on the lane, key in the
+// register) converted pairwise to bf16 IS the B operand of the PV product; its k order inside a 16-key step is
+// 16 s + 8 (j >> 2) + 4 half + (j & 3), so the A operand (V^T) is read as two 4-key groups per step (att_read_vt).  Softmax in
+// fp32 with exp2 (scale * log2 e folded in).  D changes the row width of the LDS images (att_kswz / att_vswz / att_tr_off),
+// the loader passes per tile (one chunk per thread and pass: 1 at D = 32, 2 at D = 64), NS, NO and the score of a dead key; at
+// twice the head width a score tile feeds twice the matrix work per exponential.
 // =================================================================================================
-// score of a key outside the softmax in attention_bf16_d64_kernel: -2^100 (below the running max's start, -1e30).  The exponent is
-// fma(s, c, -m c) with c = 0.125 log2 e: for s = m = -1e30 that is the rounding error of the product, about 1e22 -- exp2 of it is
-// inf where it is positive, and a leading tile with every key padded would poison the row.  s c is exact at a power of two, so a
-// padded key gives fma(s, c, -m c) <= -0.27e30 c: p = 0
-constexpr float ATT_DEAD64 = -1267650600228229401496703205376.0f;
-__device__ __forceinline__ int att_kswz64(int r, int c) { return r * 8 + (c ^ ((r >> 1) & 7)); }     // 16-byte chunk c of key r
-__device__ __forceinline__ int att_vswz64(int r, int c) { return r * 8 + (c ^ (((r >> 1) & 1) << 2)); }
-// byte offset of this lane's transposed V read for output tile o (as attention_bf16_kernel's tr_off, 128-byte rows; the 64-byte
-// half holding tile o is o ^ (bit 1 of the lane's key row q = (lane & 15) >> 2))
-__device__ __forceinline__ int att_tr_off64(int lane, int o) {
-    return (((lane >> 5) * 4 + ((lane & 15) >> 2)) * 128) + (((o ^ ((lane >> 3) & 1)) * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2);
-}
+// score of a key outside the softmax (beyond Lk, or padded) in attention_bf16_kernel.  D = 64: -2^100, below the running max's
+// start, -1e30.  The exponent is fma(s, c, -m c) with c = scale * log2 e: for s = m = -1e30 that is the rounding error of the
+// product, about 1e22 -- exp2 of it is inf where it is positive, and a leading tile with every key padded would poison the row.
+// At D = 64 (c = 0.125 log2 e) s c is exact at a power of two, so a padded key gives fma(s, c, -m c) <= -0.27e30 c: p = 0.
+// D = 32 keeps -1e30, the value its outputs have always been computed with (tests/width_ref.py restates both constants), so
+// there a leading 64-key tile that is all padding is not covered by this argument.
+template <int D> constexpr float ATT_DEAD_BF16 = D == 32 ? -1e30f : -1267650600228229401496703205376.0f;
 
-__global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* __restrict__ Q, int ldq,
-                                                                 const bf16_t* __restrict__ K, int ldk,
-                                                                 const bf16_t* __restrict__ V, int ldv,
-                                                                 bf16_t* __restrict__ O, int ldo, int Lq, int Lk, float c_log2,
-                                                                 const unsigned char* __restrict__ key_mask) {
-    constexpr int KT = 64, D = 64;
+template <int D>
+__global__ __launch_bounds__(256) void attention_bf16_kernel(const bf16_t* __restrict__ Q, int ldq,
+                                                             const bf16_t* __restrict__ K, int ldk,
+                                                             const bf16_t* __restrict__ V, int ldv,
+                                                             bf16_t* __restrict__ O, int ldo, int Lq, int Lk, float c_log2,
+                                                             const unsigned char* __restrict__ key_mask) {
+    static_assert(D == 32 || D == 64, "head dim 32 or 64");
+    constexpr int KT = 64;
     constexpr int NC = D / 8;            // 16-byte chunks per K / V row
     constexpr int NS = D / 16;           // 16-channel k-steps of S^T = K . Q^T
     constexpr int NO = D / 32;           // 32-channel output tiles
     constexpr int RPP = 256 / NC;        // key rows staged per loader pass
     constexpr int NLD = KT / RPP;        // loader passes per tile
     __shared__ __align__(16) uint4 Ks[2][KT * NC];
-    // V row-major with its 64-byte halves swapped as att_vswz64 places them, read transposed (ds_read_b64_tr_b16) as in attention_bf16_kernel
-    __shared__ __align__(16) uint4 Vs[2][KT * NC];
+    __shared__ __align__(16) uint4 Vs[2][KT * NC];     // row-major as att_vswz places the chunks, read transposed (att_read_vt)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
     const int h = blockIdx.y, b = blockIdx.z;
@@ -576,7 +316,7 @@ __global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* _
         for (int st = 0; st < NS; st++)
             qf[st] = (q < Lq) ? *reinterpret_cast<const uint4*>(Qb + (size_t)q * ldq + 16 * st + 8 * half) : uint4{0u, 0u, 0u, 0u};
     }
-    const int lk = tid >> 3, lc = tid & 7;         // loader: key row of the tile, 8-channel chunk
+    const int lk = tid / NC, lc = tid % NC;        // loader: key row of the tile, 8-channel chunk
     auto load_kv = [&](int kt, uint4 (&kr)[NLD], uint4 (&vr)[NLD]) {
 #pragma unroll
         for (int pss = 0; pss < NLD; pss++) {
@@ -593,14 +333,13 @@ __global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* _
 #pragma unroll
         for (int pss = 0; pss < NLD; pss++) {
             const int r = lk + pss * RPP;
-            Ks[buf][att_kswz64(r, lc)] = kr[pss];
-            Vs[buf][att_vswz64(r, lc)] = vr[pss];
+            Ks[buf][att_kswz<D>(r, lc)] = kr[pss];
+            Vs[buf][att_vswz<D>(r, lc)] = vr[pss];
         }
     };
-    typedef short tr4_t __attribute__((ext_vector_type(4)));
     int tr_off[NO];
 #pragma unroll
-    for (int o = 0; o < NO; o++) tr_off[o] = att_tr_off64(lane, o);
+    for (int o = 0; o < NO; o++) tr_off[o] = att_tr_off<D>(lane, o);
 
     floatx16 oacc[NO];
 #pragma unroll
@@ -623,11 +362,7 @@ __global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* _
             for (int r = 0; r < 16; r++) s[jh][r] = 0.0f;
             const int key = jh * 32 + col;
 #pragma unroll
-            for (int st = 0; st < NS; st++) {
-                const uint4 kf = Ks[cur][att_kswz64(key, 2 * st + half)];
-                s[jh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, kf), __builtin_bit_cast(bf16x8_t, qf[st]),
-                                                                s[jh], 0, 0, 0);
-            }
+            for (int st = 0; st < NS; st++) att_mma(s[jh], Ks[cur][att_kswz<D>(key, 2 * st + half)], qf[st]);
         }
         const int kbase = kt * KT;
         if (kbase + KT > Lk || key_mask) {
@@ -637,7 +372,7 @@ __global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* _
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const int k = jh * 32 + acc_row(r, half);
-                    if (kbase + k >= Lk || (mk && mk[k])) s[jh][r] = ATT_DEAD64;
+                    if (kbase + k >= Lk || (mk && mk[k])) s[jh][r] = ATT_DEAD_BF16<D>;
                 }
         }
         float mx = s[0][0];
@@ -672,17 +407,10 @@ __global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* _
 #pragma unroll
                 for (int e = 0; e < 4; e++)
                     pw[e] = pack_bf16x2(s[jh][8 * st + 2 * e], s[jh][8 * st + 2 * e + 1]);
-                typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
 #pragma unroll
-                for (int o = 0; o < NO; o++) {
-                    const char* vb = reinterpret_cast<const char*>(&Vs[cur][0]) + (jh * 32 + 16 * st) * 2 * D + tr_off[o];
-                    const tr4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb));                  // keys 4 half .. + 3 of the step
-                    const tr4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 2 * D));      // keys 8 + 4 half .. + 3
-                    const uint2 lo = __builtin_bit_cast(uint2, lo4), hi = __builtin_bit_cast(uint2, hi4);
-                    const uint4 vf = uint4{lo.x, lo.y, hi.x, hi.y};
-                    oacc[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vf),
-                                                                      __builtin_bit_cast(bf16x8_t, uint4{pw[0], pw[1], pw[2], pw[3]}), oacc[o], 0, 0, 0);
-                }
+                for (int o = 0; o < NO; o++)
+                    att_mma(oacc[o], att_read_vt<D>(reinterpret_cast<const char*>(&Vs[cur][0]) + (jh * 32 + 16 * st) * 2 * D + tr_off[o]),
+                            uint4{pw[0], pw[1], pw[2], pw[3]});
             }
         if (kt + 1 < ntiles) store_kv(cur ^ 1, kr, vr);
         __syncthreads();
@@ -690,31 +418,44 @@ __global__ __launch_bounds__(256) void attention_bf16_d64_kernel(const bf16_t* _
     const int q = q0 + col;
     if (q < Lq) {
         const float inv = 1.0f / l_run;
-        bf16_t* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
+        auto* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
 #pragma unroll
         for (int o = 0; o < NO; o++)
 #pragma unroll
             for (int g = 0; g < 4; g++)
-                st4(Ob + o * 32 + 8 * g + 4 * half,
+                st4(Ob + o * 32 + 8 * g + 4 * half,      // channels o * 32 + acc_row(4 g .. 4 g + 3, half)
                     float4{oacc[o][4 * g + 0] * inv, oacc[o][4 * g + 1] * inv, oacc[o][4 * g + 2] * inv, oacc[o][4 * g + 3] * inv});
     }
 }
 
-__global__ __launch_bounds__(256) void attention_x3_d64_kernel(const float* __restrict__ Q, int ldq,
-                                                               const float* __restrict__ K, int ldk,
-                                                               const float* __restrict__ V, int ldv,
-                                                               float* __restrict__ O, int ldo, int Lq, int Lk, float scale,
-                                                               const unsigned char* __restrict__ key_mask) {
-    // 32-key tiles: the K / V images (three bf16 planes each, double buffered) stay at attention_x3_kernel's 48 KiB, so three
-    // workgroups still share a CU; 256 chunks of 8 values per tile, one per thread
-    constexpr int D = 64, KT = 32;
-    static_assert(KT == 32, "one 32-key block per tile (the key mask below selects on s[0] only)");
+// =================================================================================================
+// Fused attention for fp32 operands on the bf16 matrix instruction (the fp32 detector), head dim D = 32 or 64: the dataflow of
+// attention_bf16_kernel with every product taken through the exact three-way bf16 split of conv_gemm.hip (a = hi + mid + lo
+// by truncation, six bf16 x bf16 products per fp32 product, fp32 accumulate; max error vs float64 0.8-1.4e-7 of sum |a b|,
+// the fp32 matrix instruction's own chain 1.1-1.9e-7).  K and V tiles are split once when they are staged (three bf16 planes
+// each in LDS, laid out as the bf16 kernel's), the pre-scaled query fragment is split once per workgroup, the probabilities
+// -- fp32 in the S^T accumulators -- are split in registers and are the B operand of the PV product as they stand.  At
+// D = 32, per 64-key tile and wave 48 matrix instructions of 32 cycles against 64 of 64 on v_mfma_f32_32x32x2_f32.  Softmax
+// as in the fp32 kernel (q pre-scaled, __expf).  D changes the LDS rows, NS, NO and the key tile: KT = 2048 / D keys, 64 at
+// D = 32 and 32 at D = 64, so that the K / V images (three planes each, double buffered) stay at 48 KiB and three workgroups
+// share a CU; that is 256 chunks of 8 values per tile, one per thread.  With the key tile goes the form of the key mask
+// (see there).
+// =================================================================================================
+template <int D>
+__global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restrict__ Q, int ldq,
+                                                           const float* __restrict__ K, int ldk,
+                                                           const float* __restrict__ V, int ldv,
+                                                           float* __restrict__ O, int ldo, int Lq, int Lk, float scale,
+                                                           const unsigned char* __restrict__ key_mask) {
+    static_assert(D == 32 || D == 64, "head dim 32 or 64");
+    constexpr int KT = 2048 / D;
     constexpr int NJ = KT / 32;          // 32-key blocks per tile
     constexpr int NC = D / 8;            // 16-byte (bf16) chunks per K / V row
+    static_assert(KT * NC == 256, "one 8-value chunk per thread and tile");
     constexpr int NS = D / 16;           // 16-channel k-steps of S^T = K . Q^T
     constexpr int NO = D / 32;           // 32-channel output tiles
     __shared__ __align__(16) uint4 Ks[2][3][KT * NC];
-    __shared__ __align__(16) uint4 Vs[2][3][KT * NC];     // V's three planes row-major, read transposed (ds_read_b64_tr_b16) as in attention_bf16_kernel
+    __shared__ __align__(16) uint4 Vs[2][3][KT * NC];     // V's three planes, each as attention_bf16_kernel's V tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
     const int h = blockIdx.y, b = blockIdx.z;
@@ -738,7 +479,7 @@ __global__ __launch_bounds__(256) void attention_x3_d64_kernel(const float* __re
             att_split8(a, c, qh[st], qm[st], ql[st]);
         }
     }
-    const int lk = tid >> 3, lc = tid & 7;         // loader: key row of the tile, 8-channel chunk
+    const int lk = tid / NC, lc = tid % NC;        // loader: key row of the tile, 8-channel chunk
     auto load_kv = [&](int kt, float4 (&kr)[2], float4 (&vr)[2]) {
         const int key = kt * KT + lk;
         if (key < Lk) {
@@ -752,17 +493,14 @@ __global__ __launch_bounds__(256) void attention_x3_d64_kernel(const float* __re
         uint4 p[3];
         att_split8(kr[0], kr[1], p[0], p[1], p[2]);
 #pragma unroll
-        for (int pl = 0; pl < 3; pl++) Ks[buf][pl][att_kswz64(lk, lc)] = p[pl];
+        for (int pl = 0; pl < 3; pl++) Ks[buf][pl][att_kswz<D>(lk, lc)] = p[pl];
         att_split8(vr[0], vr[1], p[0], p[1], p[2]);
 #pragma unroll
-        for (int pl = 0; pl < 3; pl++) Vs[buf][pl][att_vswz64(lk, lc)] = p[pl];
+        for (int pl = 0; pl < 3; pl++) Vs[buf][pl][att_vswz<D>(lk, lc)] = p[pl];
     };
-    typedef short tr4_t __attribute__((ext_vector_type(4)));
-    typedef tr4_t __attribute__((address_space(3))) * lds_tr_ptr;
     int tr_off[NO];
 #pragma unroll
-    for (int o = 0; o < NO; o++) tr_off[o] = att_tr_off64(lane, o);
-#define ODAM_MMA(acc, a, bq) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, bq), acc, 0, 0, 0)
+    for (int o = 0; o < NO; o++) tr_off[o] = att_tr_off<D>(lane, o);
 
     floatx16 oacc[NO];
 #pragma unroll
@@ -786,27 +524,41 @@ __global__ __launch_bounds__(256) void attention_x3_d64_kernel(const float* __re
             const int key = jh * 32 + col;
 #pragma unroll
             for (int st = 0; st < NS; st++) {
-                const int idx = att_kswz64(key, 2 * st + half);
+                const int idx = att_kswz<D>(key, 2 * st + half);
                 const uint4 kh = Ks[cur][0][idx], km = Ks[cur][1][idx], kl = Ks[cur][2][idx];
-                ODAM_MMA(s[jh], kl, qh[st]); ODAM_MMA(s[jh], km, qm[st]); ODAM_MMA(s[jh], kh, ql[st]);     // smallest products first
-                ODAM_MMA(s[jh], km, qh[st]); ODAM_MMA(s[jh], kh, qm[st]);
-                ODAM_MMA(s[jh], kh, qh[st]);
+                att_mma(s[jh], kl, qh[st]); att_mma(s[jh], km, qm[st]); att_mma(s[jh], kh, ql[st]);     // smallest products first
+                att_mma(s[jh], km, qh[st]); att_mma(s[jh], kh, qm[st]);
+                att_mma(s[jh], kh, qh[st]);
             }
         }
         const int kbase = kt * KT;
-        // keys beyond Lk and padded keys: one bit per accumulator register, gathered first and applied by selects (written
-        // inside the branch, the stores to the accumulator were lost in code generation at this tile size)
-        unsigned dead = 0u;
-        if (kbase + KT > Lk || key_mask) {
+        // keys beyond Lk and padded keys, in one form per tile size, and both are needed.  One 32-key block per tile: one bit per
+        // accumulator register, gathered first and applied by selects -- written inside the branch, the stores to the accumulator
+        // were lost in code generation at this tile size ("Kernels (detr_kernels.hip)").  Two blocks: written inside
+        // the branch, which costs nothing on an interior tile without a mask; the selects always execute, about 125 vector
+        // instructions per key tile at this size.
+        if constexpr (NJ == 1) {
+            unsigned dead = 0u;
+            if (kbase + KT > Lk || key_mask) {
+                const unsigned char* mk = key_mask ? key_mask + (size_t)b * Lk + kbase : nullptr;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int k = acc_row(r, half);
+                    if (kbase + k >= Lk || (mk && mk[k])) dead |= 1u << r;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; r++) s[0][r] = ((dead >> r) & 1u) ? -1e30f : s[0][r];
+        } else if (kbase + KT > Lk || key_mask) {
             const unsigned char* mk = key_mask ? key_mask + (size_t)b * Lk + kbase : nullptr;
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int k = acc_row(r, half);
-                if (kbase + k >= Lk || (mk && mk[k])) dead |= 1u << r;
-            }
-        }
+            for (int jh = 0; jh < NJ; jh++)
 #pragma unroll
-        for (int r = 0; r < 16; r++) s[0][r] = ((dead >> r) & 1u) ? -1e30f : s[0][r];
+                for (int r = 0; r < 16; r++) {
+                    const int k = jh * 32 + acc_row(r, half);
+                    if (kbase + k >= Lk || (mk && mk[k])) s[jh][r] = -1e30f;
+                }
+        }
         float mx = s[0][0];
 #pragma unroll
         for (int jh = 0; jh < NJ; jh++)
@@ -842,75 +594,59 @@ __global__ __launch_bounds__(256) void attention_x3_d64_kernel(const float* __re
                 for (int o = 0; o < NO; o++) {
                     uint4 vf[3];
 #pragma unroll
-                    for (int pl = 0; pl < 3; pl++) {
-                        const char* vb = reinterpret_cast<const char*>(&Vs[cur][pl][0]) + (jh * 32 + 16 * st) * 2 * D + tr_off[o];
-                        const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb)));
-                        const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vb + 8 * 2 * D)));
-                        vf[pl] = uint4{lo.x, lo.y, hi.x, hi.y};
-                    }
-                    ODAM_MMA(oacc[o], vf[2], ph); ODAM_MMA(oacc[o], vf[1], pm); ODAM_MMA(oacc[o], vf[0], pl_);
-                    ODAM_MMA(oacc[o], vf[1], ph); ODAM_MMA(oacc[o], vf[0], pm);
-                    ODAM_MMA(oacc[o], vf[0], ph);
+                    for (int pl = 0; pl < 3; pl++)
+                        vf[pl] = att_read_vt<D>(reinterpret_cast<const char*>(&Vs[cur][pl][0]) + (jh * 32 + 16 * st) * 2 * D + tr_off[o]);
+                    att_mma(oacc[o], vf[2], ph); att_mma(oacc[o], vf[1], pm); att_mma(oacc[o], vf[0], pl_);
+                    att_mma(oacc[o], vf[1], ph); att_mma(oacc[o], vf[0], pm);
+                    att_mma(oacc[o], vf[0], ph);
                 }
             }
         if (kt + 1 < ntiles) store_kv(cur ^ 1, kr, vr);
         __syncthreads();
     }
-#undef ODAM_MMA
     const int q = q0 + col;
     if (q < Lq) {
         const float inv = 1.0f / l_run;
-        float* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
+        auto* Ob = O + ((size_t)b * Lq + q) * ldo + h * D;
 #pragma unroll
         for (int o = 0; o < NO; o++)
 #pragma unroll
             for (int g = 0; g < 4; g++)
-                st4(Ob + o * 32 + 8 * g + 4 * half,
+                st4(Ob + o * 32 + 8 * g + 4 * half,      // channels o * 32 + acc_row(4 g .. 4 g + 3, half)
                     float4{oacc[o][4 * g + 0] * inv, oacc[o][4 * g + 1] * inv, oacc[o][4 * g + 2] * inv, oacc[o][4 * g + 3] * inv});
     }
+}
+
+template <int D>
+static int launch_attention_hd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                               dim3 grid, int Lq, int Lk, int dtype, hipStream_t stream, const unsigned char* key_mask) {
+    // sqrt(1/D) as torch computes it in float64, then float32 (F.multi_head_attention_forward: q * float(head_dim) ** -0.5)
+    const float scale = D == 32 ? (float)0.1767766952966369 : 0.125f;
+    const bool bf16_mfma = odam_cfg::get(odam_cfg::ATT_BF16_MFMA) != 0;   // 0: keep bf16 mode on the fp32-instruction kernel
+    // fp32: products through the exact three-way bf16 split (ODAM_ATT_X3=0 keeps the fp32 matrix instruction)
+    const bool x3 = odam_cfg::get(odam_cfg::ATT_X3) != 0;
+    if (dtype == 1 && bf16_mfma && (ldq % 8) == 0 && (ldk % 8) == 0 && (ldv % 8) == 0 && (ldo % 4) == 0) {
+        hipLaunchKernelGGL(attention_bf16_kernel<D>, grid, dim3(256), 0, stream, (const bf16_t*)Q, ldq, (const bf16_t*)K, ldk,
+                           (const bf16_t*)V, ldv, (bf16_t*)O, ldo, Lq, Lk, scale * 1.44269504088896341f, key_mask);
+    } else if (dtype == 0 && x3 && (ldq % 4) == 0 && (ldk % 4) == 0 && (ldv % 4) == 0 && (ldo % 4) == 0) {
+        hipLaunchKernelGGL(attention_x3_kernel<D>, grid, dim3(256), 0, stream, (const float*)Q, ldq, (const float*)K, ldk,
+                           (const float*)V, ldv, (float*)O, ldo, Lq, Lk, scale, key_mask);
+    } else {
+#define ODAM_K(T, ...) hipLaunchKernelGGL((attention_kernel<T, D>), grid, dim3(256), 0, stream, (const T*)Q, ldq, (const T*)K, ldk, (const T*)V, ldv, (T*)O, ldo, Lq, Lk, scale, key_mask)
+        ODAM_DISPATCH(dtype, ODAM_K, 0);
+#undef ODAM_K
+    }
+    ODAM_HIP(hipGetLastError());
+    return 0;
 }
 
 int launch_attention(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                      int B, int H, int Lq, int Lk, int dtype, hipStream_t stream, const unsigned char* key_mask, int head_dim) {
     if (Lq <= 0 || Lk <= 0 || B <= 0) return 0;
     if (head_dim != 32 && head_dim != 64) return odam_fail(1, "launch_attention: head dim 32 or 64 only");
-    dim3 grid((Lq + 127) / 128, H, B);
-    // sqrt(1/D) as torch computes it in float64, then float32 (F.multi_head_attention_forward: q * float(head_dim) ** -0.5)
-    const float scale = head_dim == 32 ? (float)0.1767766952966369 : 0.125f;
-    const bool bf16_mfma = odam_cfg::get(odam_cfg::ATT_BF16_MFMA) != 0;   // 0: keep bf16 mode on the fp32-instruction kernel
-    if (dtype == 1 && bf16_mfma && (ldq % 8) == 0 && (ldk % 8) == 0 && (ldv % 8) == 0 && (ldo % 4) == 0) {
-        if (head_dim == 32)
-            hipLaunchKernelGGL(attention_bf16_kernel, grid, dim3(256), 0, stream, (const bf16_t*)Q, ldq, (const bf16_t*)K, ldk,
-                               (const bf16_t*)V, ldv, (bf16_t*)O, ldo, Lq, Lk, scale * 1.44269504088896341f, key_mask);
-        else
-            hipLaunchKernelGGL(attention_bf16_d64_kernel, grid, dim3(256), 0, stream, (const bf16_t*)Q, ldq, (const bf16_t*)K, ldk,
-                               (const bf16_t*)V, ldv, (bf16_t*)O, ldo, Lq, Lk, scale * 1.44269504088896341f, key_mask);
-        ODAM_HIP(hipGetLastError());
-        return 0;
-    }
-    // fp32: products through the exact three-way bf16 split (ODAM_ATT_X3=0 keeps the fp32 matrix instruction)
-    const bool x3 = odam_cfg::get(odam_cfg::ATT_X3) != 0;
-    if (dtype == 0 && x3 && (ldq % 4) == 0 && (ldk % 4) == 0 && (ldv % 4) == 0 && (ldo % 4) == 0) {
-        if (head_dim == 32)
-            hipLaunchKernelGGL(attention_x3_kernel, grid, dim3(256), 0, stream, (const float*)Q, ldq, (const float*)K, ldk,
-                               (const float*)V, ldv, (float*)O, ldo, Lq, Lk, scale, key_mask);
-        else
-            hipLaunchKernelGGL(attention_x3_d64_kernel, grid, dim3(256), 0, stream, (const float*)Q, ldq, (const float*)K, ldk,
-                               (const float*)V, ldv, (float*)O, ldo, Lq, Lk, scale, key_mask);
-        ODAM_HIP(hipGetLastError());
-        return 0;
-    }
-    if (head_dim == 32) {
-#define ODAM_K(T, ...) hipLaunchKernelGGL((attention_kernel<T, 32>), grid, dim3(256), 0, stream, (const T*)Q, ldq, (const T*)K, ldk, (const T*)V, ldv, (T*)O, ldo, Lq, Lk, scale, key_mask)
-        ODAM_DISPATCH(dtype, ODAM_K, 0);
-#undef ODAM_K
-    } else {
-#define ODAM_K(T, ...) hipLaunchKernelGGL((attention_kernel<T, 64>), grid, dim3(256), 0, stream, (const T*)Q, ldq, (const T*)K, ldk, (const T*)V, ldv, (T*)O, ldo, Lq, Lk, scale, key_mask)
-        ODAM_DISPATCH(dtype, ODAM_K, 0);
-#undef ODAM_K
-    }
-    ODAM_HIP(hipGetLastError());
-    return 0;
+    const dim3 grid((Lq + 127) / 128, H, B);
+    return head_dim == 32 ? launch_attention_hd<32>(Q, ldq, K, ldk, V, ldv, O, ldo, grid, Lq, Lk, dtype, stream, key_mask)
+                          : launch_attention_hd<64>(Q, ldq, K, ldk, V, ldv, O, ldo, grid, Lq, Lk, dtype, stream, key_mask);
 }
 
 // head dimension 64, fp32 (associator GNN: scores / 64**0.5, src/models/associator.py:47-56)

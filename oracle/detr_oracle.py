@@ -271,7 +271,7 @@ def detr_forward(sd, img, blocks=(3, 4, 6, 3), nheads=8, enc_layers=6, dec_layer
 # (odam_amd/csrc/detr_model.hip forward_impl with dtype 1): the image, every weight matrix, every conv / linear output
 # after its fp32 epilogue (x scale + bias (+ residual) (ReLU)), the attention probabilities as the PV operand and the
 # attention output, both LayerNorm outputs (y and y + pos, each rounded from the fp32 value).  Accumulation, FrozenBN
-# scale / bias, biases, softmax (per 64-key tile, running max, exp2 with the scale folded in: attention_bf16_kernel) and
+# scale / bias, biases, softmax (per 64-key tile, running max, exp2 with the scale folded in: attention_bf16_kernel<32>) and
 # LayerNorm statistics are fp32, the head outputs are not rounded.  What still differs from the kernel is the order of
 # fp32 summation inside a contraction, i.e. a last-bit difference that occasionally flips one bf16 rounding.
 # The reference itself has no bf16 mode (src/models/detr.py:49-94 runs fp32); this restatement is the checker of OUR bf16

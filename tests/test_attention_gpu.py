@@ -37,7 +37,7 @@ SENTINEL = -448.0                                    # exact in fp32 and bf16, f
 C_X3 = 2.5
 C_F32 = 4.5
 C_D64 = 4.0
-# attention_bf16_kernel vs the bf16-faithful oracle: share of the outputs that differ (one-ulp ties), per logit regime, about 2x
+# attention_bf16_kernel<32> vs the bf16-faithful oracle: share of the outputs that differ (one-ulp ties), per logit regime, about 2x
 # the measured share (attention.bf16.oracle_tie_share.*): randn 6.0e-4, near one-hot 1.2e-4, duplicated keys 6.4e-5, +60 offset
 # 0.059 (logits of ~340 / sqrt(32): their fp32 summation noise moves P across bf16 rounding boundaries).  A kernel whose P is not
 # rounded to bf16 (the fp32-instruction kernel on bf16 storage) differs in 0.27-0.40 of the outputs, 0.061 near one-hot.
@@ -213,7 +213,7 @@ def _oracle_diff(got_b, want, v, H=8):
 
 
 def _bf16_vs_oracle(got, q, k, v, mask, tag, regime, measured):
-    """attention_bf16_kernel's bits against oracle _attention_b on the same (bf16) inputs: elements off by one ulp no more than
+    """attention_bf16_kernel<32>'s bits against oracle _attention_b on the same (bf16) inputs: elements off by one ulp no more than
     the measured share of the regime, larger differences no more than one probability rounding flip explains.  Recorded beside
     it: the same comparison for the oracle without the fma exponent, and for the fp32-instruction kernel on bf16 storage, whose P
     is not rounded (what the share cap tells apart)."""

@@ -30,7 +30,7 @@ C_F32_64 = 2.0
 # the fp32-logit term of the bf16 bounds (tests/test_attention_gpu.py::_bf16_checks, there C_F32 = 4.5): measured bound ratios 0.42
 # (bf16 instruction) and 0.99 (fp32 instruction on bf16 storage, where the output rounding reaches its worst case)
 C_BF16_LOGIT = 6.0
-# attention_bf16_d64_kernel against width_ref.attention_b: share of one-ulp ties per logit regime, about 2x the measured share
+# attention_bf16_kernel<64> against width_ref.attention_b: share of one-ulp ties per logit regime, about 2x the measured share
 # (randn 8.7e-4, sharp 2.0e-5, dup 5.9e-5, offset 0.058)
 TIE_SHARE_64 = {"randn": 2e-3, "sharp": 2.5e-4, "dup": 1.5e-4, "offset": 0.12}
 C_LN = 18.0                  # as tests/test_attention_gpu.py; measured 3.4 (C = 128) .. 11.5 (C = 384)
@@ -181,7 +181,7 @@ def _f32_ratio(got, o64, A, vmax, H):
 
 @pytest.mark.parametrize("case", CASES, ids=_ids)
 def test_attention_d64_fp32_vs_float64(case, measured):
-    """attention_x3_d64_kernel (att.x3 = 1, the default) and attention_kernel<float, 64> with the mask (att.x3 = 0)"""
+    """attention_x3_kernel<64> (att.x3 = 1, the default) and attention_kernel<float, 64> with the mask (att.x3 = 0)"""
     B, Lq, Lk, layout, regime, E, masked = case
     H = E // 64
     q, k, v = _qkv(B, Lq, Lk, E, regime, seed=Lq * 1000 + Lk + E)
@@ -199,7 +199,7 @@ def test_attention_d64_fp32_vs_float64(case, measured):
 
 @pytest.mark.parametrize("case", CASES, ids=_ids)
 def test_attention_d64_bf16_vs_float64_and_restatement(case, measured):
-    """attention_bf16_d64_kernel (att.bf16_mfma = 1) and attention_kernel<bf16, 64> (= 0) on bf16 inputs against float64 with the
+    """attention_bf16_kernel<64> (att.bf16_mfma = 1) and attention_kernel<bf16, 64> (= 0) on bf16 inputs against float64 with the
     bounds of tests/test_attention_gpu.py::_bf16_checks; the first also against width_ref.attention_b, one-ulp ties only"""
     B, Lq, Lk, layout, regime, E, masked = case
     H = E // 64

@@ -45,15 +45,15 @@ def detr_forward(sd, img, blocks=(3, 4, 6, 3), nheads=8, enc_layers=6, dec_layer
 
 
 def attention_b(q, k, v, nheads, tile=64, key_mask=None, fma=True):
-    """O._attention_b with the scale of the head dim E / nheads folded into the exponent (attention_bf16_kernel at D = 32,
-    attention_bf16_d64_kernel at D = 64): 64-key tiles, running max, P rounded to bf16 as the PV operand, O rounded."""
+    """O._attention_b with the scale of the head dim E / nheads folded into the exponent (attention_bf16_kernel<D>,
+    D = 32 or 64): 64-key tiles, running max, P rounded to bf16 as the PV operand, O rounded."""
     B, Lq, E = q.shape
     Lk, D = k.shape[1], E // nheads
     qh = q.reshape(B, Lq, nheads, D).permute(0, 2, 1, 3)
     kh = k.reshape(B, Lk, nheads, D).permute(0, 2, 1, 3)
     vh = v.reshape(B, Lk, nheads, D).permute(0, 2, 1, 3)
     c = head_scale(D) * torch.tensor(1.44269504088896341, dtype=torch.float32)
-    dead = -1e30 if D == 32 else -2.0 ** 100      # a padded key's score (attention_bf16_d64_kernel: ATT_DEAD64)
+    dead = -1e30 if D == 32 else -2.0 ** 100      # a padded key's score (attention_bf16_kernel<D>: ATT_DEAD_BF16<D>)
     m = torch.full((B, nheads, Lq, 1), -1e30)
     l = torch.zeros(B, nheads, Lq, 1)
     o = torch.zeros(B, nheads, Lq, D)

@@ -4,7 +4,7 @@
    python tools/attention_timing.py [--batch 32 --tokens 850 --configs 256:8 256:4 512:8 --dtypes fp32 bf16 --iters 50]
 
 Q and K sit in one [B L, 2E] buffer and V in [B L, E], as the encoder has them.  One JSON line per (E, heads, dtype): the median
-over 5 repeats of the mean time of --iters back-to-back launches (events around each repeat), and TFLOP/s = 4 B H L^2 d / t
+over 5 repeats of the mean time of --iters back-to-back launches (events around each repeat), the repeats' [min, max], and TFLOP/s = 4 B H L^2 d / t
 (QK^T and PV, 2 flop per multiply-add)."""
 import argparse
 import ctypes
@@ -53,7 +53,8 @@ def main():
                 reps.append(e0.elapsed_time(e1) * 1e3 / a.iters)
             us = statistics.median(reps)
             print(json.dumps({"hidden_dim": E, "nheads": H, "head_dim": D, "dtype": dt, "batch": B, "tokens": L,
-                              "us_per_launch": round(us, 1), "tflops": round(4.0 * B * H * L * L * D / us / 1e6, 1),
+                              "us_per_launch": round(us, 1), "us_range": [round(min(reps), 1), round(max(reps), 1)],
+                              "tflops": round(4.0 * B * H * L * L * D / us / 1e6, 1),
                               "config": _lib.config().get("att.x3" if dt == "fp32" else "att.bf16_mfma")}), flush=True)
 
 
