@@ -154,23 +154,56 @@ def _device_scene(data, img_names):
     return tracks, [t[:, :14] for t in tracks], boxes, cls
 
 
-def _device_merge(datas, img_names_list, fitter, want_rows14):
+def _device_merge(datas, img_names_list, fitter, want_rows14, rows=None):
     """the three device steps for the scenes _device_scene accepts: ONE IoU launch, ONE clustering launch, ONE assembly pass, ONE small
     copy back.  Returns (scenes, picked, res, head): scenes[k] = _device_scene's answer or None, picked = indices of the scenes that
-    went to the device (in launch order), res = SqFitter.merge_assemble's dict, head = its "head" on the host."""
+    went to the device (in launch order), res = SqFitter.merge_assemble's dict, head = its "head" on the host.
+    rows: for ONE scene, a packed block of its tracks' rows that is on the device already (track_store.TrackRows.packed(): the rows
+    pass 1 was fitted from), used instead of the concatenate and the upload."""
     from . import evaluate
     fitter = evaluate._default_fitter(fitter)
     scenes = [_device_scene(d, names) for d, names in zip(datas, img_names_list)]
     picked = [k for k, s in enumerate(scenes) if s is not None]
     if not picked:
         return scenes, picked, None, None
+    if rows is not None:
+        if len(datas) != 1:
+            raise ValueError("merge: a packed block of rows stands for the tracks of ONE scene")
+        off = np.asarray(rows["row_offsets"], np.int64)
+        if not np.array_equal(np.diff(off), [len(t) for t in scenes[0][0]]):
+            raise ValueError("merge: the packed block of rows does not hold the tracks of this scene (rows per track differ)")
     r = evaluate._iou_launch([scenes[k][2] for k in picked], [scenes[k][2] for k in picked], [scenes[k][3] for k in picked],
                              [scenes[k][3] for k in picked], 2, fitter, False)
     cl = fitter.merge_cluster(r["iou3d"], r["a_off"], r["pair_off"])
-    rows = np.concatenate([t for k in picked for t in scenes[k][1]])
-    row_off = np.concatenate([[0], np.cumsum([len(t) for k in picked for t in scenes[k][1]])])
-    res = fitter.merge_assemble(cl, r["a_off"], rows, row_off, [img_names_list[k] for k in picked], want_rows14=want_rows14)
+    if rows is not None:
+        rows14, row_off = rows["rows14"], off
+    else:
+        rows14 = np.concatenate([t for k in picked for t in scenes[k][1]])
+        row_off = np.concatenate([[0], np.cumsum([len(t) for k in picked for t in scenes[k][1]])])
+    res = fitter.merge_assemble(cl, r["a_off"], rows14, row_off, [img_names_list[k] for k in picked], want_rows14=want_rows14)
     return scenes, picked, res, res["head"].cpu().numpy()
+
+
+def _gather_merged(tracks, off, src, cls, base=0):
+    """the merged [n, 82] tracks of one scene on the host: merged track i holds the rows src[off[i] .. off[i + 1] - 1] - base of
+    np.concatenate(tracks), with column 1 = cls[i]"""
+    allrows = np.concatenate(tracks)
+    merged = []
+    for i in range(len(cls)):
+        t = allrows[src[off[i]:off[i + 1]] - base]      # (fancy indexing: a copy, the caller's tracks stay as they were)
+        t[:, 1] = cls[i]
+        merged.append(t)
+    return merged
+
+
+def tracks_from_packed(block, data):
+    """The merged [n, 82] tracks merge_scenes returns for the scene, gathered on the host from merge_packed's block ("src",
+    "row_offsets", "cls": ONE small copy back) and the caller's tracks data["tracks"].  A caller that goes on from the block on the
+    device (SqFitter.prepare, track_store.TrackRows.adopt) calls this after it has enqueued that work."""
+    import torch
+    n, r = int(block["cls"].shape[0]), int(block["src"].shape[0])
+    h = torch.cat([block["row_offsets"].to(torch.int32), block["src"].to(torch.int32), block["cls"].to(torch.int32)]).cpu().numpy()
+    return _gather_merged(data["tracks"], h[:n + 1], h[n + 1:n + 1 + r], h[n + 1 + r:])
 
 
 def merge_scenes(datas, img_names_list, fitter=None):
@@ -195,13 +228,7 @@ def merge_scenes(datas, img_names_list, fitter=None):
         for q, k in enumerate(picked):
             tracks = scenes[k][0]
             if status[q] == 0:
-                allrows = np.concatenate(tracks)
-                merged = []
-                for i in range(o, o + int(n_out[q])):
-                    t = allrows[src[off[i]:off[i + 1]] - base]      # (fancy indexing: a copy, the caller's tracks stay as they were)
-                    t[:, 1] = cls[i]
-                    merged.append(t)
-                out[k] = merged
+                out[k] = _gather_merged(tracks, off[o:o + int(n_out[q]) + 1], src, cls[o:o + int(n_out[q])], base)
             o += int(n_out[q])
             base += sum(len(t) for t in tracks)
     for k, m in enumerate(out):
@@ -210,11 +237,13 @@ def merge_scenes(datas, img_names_list, fitter=None):
     return out
 
 
-def merge_packed(data, img_names, fitter=None):
+def merge_packed(data, img_names, fitter=None, rows=None):
     """One scene merged on the device and left there, for callers that go straight into SqFitter.prepare: {"rows14" [R_out, 14]
     float64 (column 1 = the merged class), "row_offsets" [n_out + 1] int32, "cls" [n_out] int32, "src" [R_out] int32 (indices into
-    np.concatenate(data["tracks"]))}, all device tensors; or None when the scene has to go down the host path (merge_scenes)."""
-    scenes, picked, res, head = _device_merge([data], [img_names], fitter, True)
+    np.concatenate(data["tracks"]))}, all device tensors; or None when the scene has to go down the host path (merge_scenes).
+    rows: the packed block pass 1 was fitted from (_device_merge), in place of the concatenate and the upload of the tracks' rows;
+    tracks_from_packed gives the host tracks of the block."""
+    scenes, picked, res, head = _device_merge([data], [img_names], fitter, True, rows=rows)
     if not picked or head[1] != 0:
         return None
     n_out, r_out = int(head[2]), int(head[3])

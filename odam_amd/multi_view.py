@@ -268,7 +268,7 @@ def _finish_dual(tracks, pre, n_iters, fitter, return_params):
     (an object whose discriminant goes negative raises AssertionError there, as sq_libs.py:129,136 does), DualQuadric results,
     bboxes_qc from compute_oriented_bbox of the 2500 ellipsoid points (run_multi_view.py:66-67) through the native box path.
     `pre`: what _host_prelude / _device_prelude return."""
-    n_objs = len(tracks)
+    n_objs = len(pre["classes"])      # (tracks may be None: optim_process(rows=...))
     fit_ids = pre["fit_ids"]
     out = None
     if fit_ids:
@@ -376,18 +376,29 @@ def _device_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prio
     float64 array of at least 14 columns -- the host path then raises what it always raised.  Class, views, counts, tgt, mask, P, translate and scales are the host path's bits; the yaw is the closed form
     atan2(sum sin, sum cos) of the same mean rotation: a float32 init row can differ by one unit in the last place of
     its angle, bboxes_dl in the last digits of a float64."""
-    import torch
     n_objs = len(tracks)
     if n_objs == 0 or not _UniqueFrames.applies(img_names):
         return None
     arrs = [np.asarray(t) for t in tracks]
     if any(a.ndim != 2 or a.shape[1] < 14 or a.dtype != np.float64 for a in arrs):
         return None      # the kernel reads float64 rows of 14 columns; the host path computes in the dtype it is given, or raises
-    lens = np.array([len(a) for a in arrs], np.int64)
     offs = np.zeros(n_objs + 1, np.int64)
-    offs[1:] = np.cumsum(lens)
+    offs[1:] = np.cumsum([len(a) for a in arrs])
     rows = np.concatenate([a[:, :14] for a in arrs]).astype(np.float64, copy=False)
+    return _prelude_from_rows(rows, offs, img_names, P_cws, img_h, img_w, representation, prior, n_views, fitter)
+
+
+def _prelude_from_rows(rows, offs, img_names, P_cws, img_h, img_w, representation, prior, n_views, fitter, check=None):
+    """_device_prelude from the upload on, shared by its two entries: `rows` [R, 14] float64 track after track -- the host array
+    _device_prelude concatenated, or a track_store.TrackRows block's rows, already on the device -- and their host offsets [n + 1].
+    check: called behind prepare's one synchronisation (the block's own status word arrives with it).  None where a track comes
+    back with a status."""
+    import torch
+    n_objs = len(offs) - 1
+    lens = np.diff(offs)
     prep = fitter.prepare(rows, offs, img_names, P_cws, img_h, img_w, representation)
+    if check is not None:
+        check()
     if prep["status"].any():
         return None
     dual = representation == "dual_quadric"
@@ -438,7 +449,7 @@ def _device_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prio
 
 
 def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representation, prior, n_iters, n_views,
-                  fitter=None, return_params=False, resume=None, return_state=False, prelude="host"):
+                  fitter=None, return_params=False, resume=None, return_state=False, prelude="host", rows=None):
     """run_multi_view.py:22-76 with the per-object fits batched on the GPU.
 
     Resumable (SqFitter.fit's state): with return_state the dict also holds "state" = {"state": [k, 32] rows, "track_ids": the k
@@ -449,16 +460,45 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
     prelude: "host" (default) builds the constraint rows and initial shapes per track in numpy / scipy; "device" builds them for
     all tracks in one launch (_device_prelude, SqFitter.prepare) and falls back to the host path for this call, with one debug log
     line, where that does not apply: frame ids that are not all different, a track the kernel refuses (no view, a class that is no
-    integer in 0..63, more than 16384 rows), no track, or a track that is not a float64 array of at least 14 columns."""
+    integer in 0..63, more than 16384 rows), no track, or a track that is not a float64 array of at least 14 columns.
+
+    rows: a packed block of track_store.TrackRows ({"rows14" [R, 14] float64 on the device, "row_offsets" host offsets, "n_tracks", ...;
+    DESIGN 6p) standing for [t[:, :14] for t in tracks]: the prelude is the device prelude run on that block -- no concatenate, no
+    upload, the same bits as prelude="device" on the same rows.  `tracks` is then only passed through to the result dict and may be
+    None -- or a callable without arguments that returns the list: it is called once, after the fit has been enqueued, so that a
+    caller's host work on the list (merge.tracks_from_packed) runs under the fit.  Where the device prelude does not apply the call
+    takes the host path if `tracks` is a host list, and raises ValueError naming the condition if it is not."""
     if prelude not in ("host", "device"):
         raise ValueError(f'prelude must be "host" or "device", got {prelude!r}')
     fitter = fitter or default_fitter()
-    n_objs = len(tracks)
+    later = tracks if rows is not None and callable(tracks) else None
+    if later is not None:
+        tracks = None
+    if rows is not None and tracks is not None and len(tracks) != rows["n_tracks"]:
+        raise ValueError(f"optim_process: rows holds {rows['n_tracks']} tracks, the list {len(tracks)}")
+    n_objs = int(rows["n_tracks"]) if tracks is None and rows is not None else len(tracks)
     res_state = res_ids = None
     if resume is not None or return_state:
         res_state, res_ids = _check_resume(resume, representation, n_objs)
     pre = None
-    if prelude == "device":
+    if rows is not None:
+        why = None
+        if n_objs == 0:
+            why = "the block holds no track"
+        elif not _UniqueFrames.applies(img_names):
+            why = "the frame ids of img_names are not all different integers inside int32"
+        else:
+            pre = _prelude_from_rows(rows["rows14"], np.asarray(rows["row_offsets"], np.int64), img_names, P_cws, img_h, img_w, representation,
+                                     prior, n_views, fitter, check=rows.get("check"))
+            if pre is None:
+                why = "a track came back from the prelude kernel with a status (no view, a class that is no integer in 0..63, too many rows)"
+        if pre is None:
+            if later is not None:
+                tracks, later = later(), None
+            if tracks is None:
+                raise ValueError("optim_process(rows=...): the device prelude does not apply -- " + why + " -- and there is no host track list to fall back on")
+            _log.debug("optim_process: the device prelude does not apply to the packed rows (%s), taking the host path", why)
+    elif prelude == "device":
         pre = _device_prelude(tracks, img_names, P_cws, img_h, img_w, representation, prior, n_views, fitter)
         if pre is None:
             _log.debug("optim_process: the device prelude does not apply to this call (%d tracks), taking the host path", n_objs)
@@ -467,7 +507,7 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
     classes, fit_ids, fit_counts = pre["classes"], pre["fit_ids"], pre["fit_counts"]
 
     if representation == "dual_quadric":
-        return _finish_dual(tracks, pre, n_iters, fitter, return_params)
+        return _finish_dual(later() if later is not None else tracks, pre, n_iters, fitter, return_params)
     points = {}
     state_out = None
     out = None
@@ -488,6 +528,8 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
         out = fitter.fit(pre["fit_init"], [classes[i] for i in fit_ids], fit_counts, pre["P"], pre["tgt"], pre["mask"],
                          n_iters=n_iters, representation=representation, prior=bool(prior), want_points=True, **more)
         state_out = out.get("state") if return_state else None
+    if later is not None:
+        tracks = later()
     inits, bboxes_dl = pre["host"]()
     params = {i: inits[i] for i in range(n_objs)}
     if fit_ids:

@@ -93,6 +93,57 @@ def _associate(proc, frame_ids, T_wcs, c0, rows):
             proc.process_frame(None, int(frame_ids[c0 + i]), T_wcs[c0 + i], detections=r)
 
 
+def map_scene(proc, tracks=None, resident_rows=False, device_merge=False, stages=None):
+    """The back end of run_scene on ONE rank: fit -> merge -> fit over `tracks` (default: proc.tracks), returning the second
+    optim_process dict (with "params" and "fitted") and filling `stages` with the seconds of fit1, merge and fit2 and the first pass's dict.
+
+    resident_rows  the tracks' rows go to the device ONCE (track_store.TrackRows.load) and stay there through the chain: pass 1 is fitted
+              from the store's block, merge.merge_packed assembles from the same block and leaves the merged rows on the device, the
+              store adopts them, pass 2 is fitted from the adopted block, and the merged host tracks (merge.tracks_from_packed) are gathered
+              while pass 2 runs -- no concatenate and no upload of track rows after the load; the device prelude and the device merge
+              are implied, and the results are theirs, bit for bit.  A list the store refuses takes the path below; a scene the device
+              merge refuses (merge._device_scene) takes the host merge, followed by a load of the merged tracks.
+    device_merge   without resident_rows: proc.merge_process(out, on_device=True), as in run_scene."""
+    import time
+    from . import merge
+    tracks = proc.tracks if tracks is None else tracks
+    t = {}
+    store = block = None
+    if resident_rows:
+        if proc._rows is None:
+            from .track_store import TrackRows
+            proc._rows = TrackRows(proc._fitter())
+        store = proc._rows
+        if store.load(tracks) is not None:
+            block = store.packed()
+    s0 = time.perf_counter()
+    if block is None:
+        out = proc.optim_process_params(tracks)
+        s1 = time.perf_counter()
+        merged = proc.merge_process(out, on_device=True) if device_merge else proc.merge_process(out)
+        s2 = time.perf_counter()
+        out2 = proc.optim_process_params(merged)
+    else:
+        out = proc.optim_process(tracks, return_params=True, rows=block)
+        s1 = time.perf_counter()
+        proc._refine_state = None      # keyed by track index (OdamProcess.merge_process drops it too)
+        packed = merge.merge_packed(out, proc.usable_frames, fitter=proc._fitter(), rows=block)
+        if packed is None:
+            merged = proc.merge_process(out)
+            block2 = store.packed() if store.load(merged) is not None else None
+            s2 = time.perf_counter()
+            out2 = proc.optim_process(merged, return_params=True, rows=block2) if block2 is not None else proc.optim_process_params(merged)
+        else:
+            store.adopt(packed)
+            s2 = time.perf_counter()
+            out2 = proc.optim_process(lambda: merge.tracks_from_packed(packed, out), return_params=True, rows=store.packed())
+    t.update(fit1=s1 - s0, merge=s2 - s1, fit2=time.perf_counter() - s2)
+    if stages is not None:
+        stages.update(t)
+        stages["first_pass"] = out
+    return out2
+
+
 def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=0, device=None, force=False, stages=None, overlap=None,
               device_select=False, device_merge=False):
     """The driver loop of run_processor.py:70-83 for one scene on the ranks of the current process group.

@@ -107,6 +107,8 @@ class OdamProcess:
         self.refine_fitter = None   # refine(): its own context, with a bias-correction table long enough for a whole scan (REFINE_MAX_ITERS)
         self._refine_state = None   # refine(): what multi_view.optim_process(return_state=True) returned last, keyed by track index
         self.device_prelude = False  # optim_process / refine with prelude=None: True builds the fits' constraint rows on the device (multi_view.optim_process, prelude="device")
+        self.resident_rows = False   # ... with prelude=None: True keeps the tracks' rows on the device between calls and uploads only the new ones (prelude="resident", track_store.TrackRows)
+        self._rows = None            # the row store, made by the first call that needs it
         self.logger = logging.getLogger('OdamProcess')
 
     # `tracks` is the reference's attribute (src/processor.py:300; a list of [n, 82] arrays, index = track id).  The fast path of
@@ -171,6 +173,8 @@ class OdamProcess:
         self._refine_state = None
         if getattr(self, "_win", None) is not None:
             self._win.reset()
+        if getattr(self, "_rows", None) is not None:
+            self._rows.reset()
         if getattr(self.associator, "iou_tracker", False):
             self._iou_tracker().reset()
 
@@ -745,17 +749,19 @@ class OdamProcess:
         the scales the prior is measured from are kept here, per track index) on the views it has now; a new track, or one that had
         too few views last time, starts cold.  Returns optim_process's dict.  Reads the tracks and nothing else: association, and
         optim_process at the end of the scan, go on as if it had never been called.  init_sequence clears the state, merge_process
-        drops it (track indices change there).  Not for representation "dual_quadric".  prelude: "host", "device" (multi_view.optim_process), or
-        None for what self.device_prelude says."""
+        drops it (track indices change there).  Not for representation "dual_quadric".  prelude: "host", "device" (multi_view.optim_process),
+        "resident" (the device prelude on the row store: only the rows the scan added since the last call are uploaded), or None for what
+        self.resident_rows / self.device_prelude say."""
         if self.representation == "dual_quadric":
             raise ValueError('refine: the "dual_quadric" fit is not resumable')
         if self.refine_fitter is None:
             self.refine_fitter = multi_view._sq.SqFitter(str(getattr(self.detector, "device", "cuda:0")), self.REFINE_MAX_ITERS)
         m = self.sequence_meta
-        out = multi_view.optim_process(self.tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
+        tracks = self.tracks
+        out = multi_view.optim_process(tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                        self.representation, prior=True, n_iters=int(n_iters), n_views=10,
                                        fitter=self.refine_fitter, return_params=return_params,
-                                       resume=self._refine_state, return_state=True, prelude=self._prelude(prelude))
+                                       resume=self._refine_state, return_state=True, **self._prelude_args(prelude, tracks, self.refine_fitter))
         # (a track fitted once is fitted every time after: its views only grow, so the new rows cover the old ones)
         self._refine_state = out.pop("state")
         return out
@@ -800,17 +806,33 @@ class OdamProcess:
 
     def _prelude(self, prelude):
         if prelude is None:
-            return "device" if self.device_prelude else "host"
+            return "resident" if self.resident_rows else "device" if self.device_prelude else "host"
         return prelude
 
-    def optim_process(self, tracks, return_params=False, prelude=None):
-        """prelude: "host", "device" (multi_view.optim_process), or None for what self.device_prelude says"""
+    def _prelude_args(self, prelude, tracks, fitter):
+        """the prelude keywords of multi_view.optim_process; "resident": the row store is brought in step with `tracks` (only rows that
+        were appended since the last call go up) and its packed block stands for them; a list the store refuses takes the device prelude"""
+        prelude = self._prelude(prelude)
+        if prelude != "resident":
+            return {"prelude": prelude}
+        if self._rows is None:
+            from .track_store import TrackRows
+            self._rows = TrackRows(fitter)
+        if self._rows.sync(tracks) is None:
+            return {"prelude": "device"}
+        return {"prelude": "device", "rows": self._rows.packed()}
+
+    def optim_process(self, tracks, return_params=False, prelude=None, rows=None):
+        """prelude: "host", "device" (multi_view.optim_process), "resident" (the device prelude on the row store, self._rows), or None for
+        what self.resident_rows / self.device_prelude say.  rows: a packed block that stands for the tracks' rows (multi_view.optim_process;
+        pipeline.map_scene passes its store's), whatever prelude says"""
         m = self.sequence_meta
         # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
         n_iters = 500 if self.representation == "dual_quadric" else 200
         return multi_view.optim_process(tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                         self.representation, prior=True, n_iters=n_iters, n_views=10,
-                                        fitter=self._fitter(), return_params=return_params, prelude=self._prelude(prelude))
+                                        fitter=self._fitter(), return_params=return_params,
+                                        **({"rows": rows} if rows is not None else self._prelude_args(prelude, tracks, self._fitter())))
 
     def optim_process_params(self, tracks):
         """optim_process + the fitted parameter rows and the fitted / not-fitted flags (what a rank sends to the others:

@@ -355,14 +355,15 @@ class SqFitter:
             out["state"] = st_out
         return out
 
-    def prepare(self, rows, row_offsets, img_names, P_cws, img_h, img_w, representation="super_quadric", thr=EDGE_THRESHOLD):
+    def prepare(self, rows, row_offsets, img_names, P_cws, img_h, img_w, representation="super_quadric", thr=EDGE_THRESHOLD, max_rows=None):
         """The prelude of a fit pass for ALL tracks in one launch (include/odam_sq.h, odam_sq_prepare_batch): views, constraint rows,
         class, detector box and initial parameters of every track.
 
         rows [R, 14] float64: the first 14 columns of every track row, track after track; row_offsets [n + 1]: track o owns rows
         row_offsets[o] .. row_offsets[o + 1] - 1 (numpy or torch, on the host or the device; offsets given on the host are checked
         and size the launch, offsets on the device are taken as they are and the launch is sized for the largest track the kernel
-        takes -- nothing is read back for them); img_names: the frame id of every image, all different; P_cws [n_img, 3, 4].
+        takes, or for max_rows, the most rows of one track, where the caller knows it (track_store.TrackRows does) -- nothing is read
+        back for them; a track with more rows than the launch is sized for gets status 3); img_names: the frame id of every image, all different; P_cws [n_img, 3, 4].
         Returns a dict: "cls", "n_obs", "n_valid", "status" [n] int32 numpy on the host -- ONE small copy, the only synchronisation
         -- and device tensors "init" ([n, 9], or [n, 5] with "half_dims" [n, 3] for "dual_quadric"; else half_dims is None), "pose"
         [n, 7] and "bboxes_dl" [n, 8, 3] float64, per view from row_offsets[o] on "view_img", "view_row", "valid" [R] int32, "tgt",
@@ -374,7 +375,7 @@ class SqFitter:
         ids, order = frame_tables(img_names)
         if torch.is_tensor(row_offsets) and row_offsets.is_cuda:
             d_off = row_offsets.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
-            max_rows = PREPARE_MAX_ROWS
+            max_rows = PREPARE_MAX_ROWS if max_rows is None else int(max_rows)
         else:
             offs = np.asarray(row_offsets.numpy() if torch.is_tensor(row_offsets) else row_offsets).astype(np.int64).reshape(-1)
             if len(offs) < 1 or offs[0] != 0 or (np.diff(offs) < 0).any() or offs[-1] != len(rows) or offs[-1] >= 2 ** 31:

@@ -1,0 +1,271 @@
+"""Device-resident track rows: what a fit pass needs of the map stays on the device between calls, and a refresh uploads only what the
+scan added since the last one.
+
+`TrackRows` keeps the first 14 columns of every track row in ARRIVAL order -- a log [N, 14] float64 and the track id of every row --
+and hands them out track after track, as SqFitter.prepare and SqFitter.merge_assemble take them: `packed()` is the block
+{"rows14", "row_offsets", "max_rows", "n_tracks"} that multi_view.optim_process(rows=...) and merge.merge_packed(rows=...) accept
+in place of the np.concatenate([t[:, :14] for t in tracks]) + upload they otherwise make on every call.  The order by track is made on
+the device (include/odam_rows.h: odam_rows_group, an LSD radix sort of the row indices on the id, and odam_rows_gather14), and only
+when rows were appended since the last time.
+
+The host keeps what it needs to decide WITHOUT reading rows back: rows per track and the marks associator.TrackWindows keeps (frame id
+of a track's first row, frame id and world x of its last).  Nothing here is on the per-frame path: the store catches up at the
+call that needs it (`sync`).
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+_VP, _CI = ctypes.c_void_p, ctypes.c_int
+# the entry points as include/odam_rows.h declares them (tests/test_track_rows_host.py holds the two together)
+ROWS_ARGTYPES = {
+    "odam_rows_group_workspace": [_CI, _CI, _VP],
+    "odam_rows_group": [_VP, _CI, _CI, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP],
+    "odam_rows_gather14": [_VP, _VP, _CI, _VP, _VP],
+}
+MAX_ROWS = 1 << 24       # ODAM_ROWS_MAX_ROWS
+MAX_TRACKS = 65536       # ODAM_ROWS_MAX_TRACKS
+CHUNK = 4096             # ODAM_ROWS_CHUNK: rows one workgroup of the sort takes
+ONE_PASS_TRACKS = 256    # up to here the sort is one 8-bit pass, beyond it two
+STATUS_OK, STATUS_BAD_ID, STATUS_BAD_COUNT = 0, 1, 2
+
+
+def _entry(name):
+    f = getattr(_lib.lib(), name)
+    if f.argtypes is None:
+        f.argtypes, f.restype = ROWS_ARGTYPES[name], ctypes.c_int
+    return f
+
+
+def group_workspace(n_rows, n_tracks):
+    """bytes of working memory odam_rows_group needs"""
+    b = ctypes.c_size_t(0)
+    _lib.check(_entry("odam_rows_group_workspace")(int(n_rows), int(n_tracks), ctypes.cast(ctypes.byref(b), _VP)), "odam_rows_group_workspace")
+    return int(b.value)
+
+
+def group(tid, n_tracks, row_off, src_out=None, status=None):
+    """odam_rows_group on device tensors, on the current stream: tid [N] int32, row_off [n_tracks + 1] int32 -> (src [N] int32, status
+    [1] int32), both on the device; nothing is read back"""
+    import torch
+    N = int(tid.shape[0])
+    dev = tid.device
+    if src_out is None:
+        src_out = torch.empty(max(N, 1), device=dev, dtype=torch.int32)
+    if status is None:
+        status = torch.zeros(1, device=dev, dtype=torch.int32)
+    nbytes = group_workspace(N, n_tracks)
+    work = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(_entry("odam_rows_group")(_lib.ptr(tid), N, int(n_tracks), _lib.ptr(row_off), _lib.ptr(src_out), _lib.ptr(status),
+                                             _lib.ptr(work), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "odam_rows_group")
+    return src_out[:N], status
+
+
+def gather14(log, src, out=None):
+    """odam_rows_gather14 on device tensors, on the current stream: out[i] = log[src[i]] on whole rows, bit for bit"""
+    import torch
+    N = int(src.shape[0])
+    if out is None:
+        out = torch.empty(max(N, 1), 14, device=log.device, dtype=torch.float64)
+    with torch.cuda.device(log.device):
+        _lib.check(_entry("odam_rows_gather14")(_lib.ptr(log), _lib.ptr(src), N, _lib.ptr(out),
+                                                ctypes.c_void_p(torch.cuda.current_stream(log.device).cuda_stream)), "odam_rows_gather14")
+    return out[:N]
+
+
+def _marks_of(tracks):
+    from .associator import TrackWindows
+    return TrackWindows._marks_of(tracks)
+
+
+def _acceptable(tracks):
+    """what multi_view._device_prelude takes: float64 arrays of at least 14 columns, none of them empty"""
+    return all(isinstance(t, np.ndarray) and t.ndim == 2 and t.shape[1] >= 14 and t.dtype == np.float64 and len(t) for t in tracks)
+
+
+class TrackRows:
+    """The row store of one sequence on `fitter`'s device (see the module text).  Counters for tests and tools: rows_uploaded (rows sent
+    from the host, in all), loads (full uploads), groupings (runs of the sort)."""
+
+    def __init__(self, fitter, capacity_rows=65536):
+        self.fitter = fitter
+        self.device = fitter.device
+        self.capacity = max(int(capacity_rows), 1)
+        self._log = self._tid = None          # [capacity, 14] float64, [capacity] int32: made at the first upload
+        self._stage = None                    # pinned staging: (rows [k, 14] float64, ids [k] int32), grown on demand
+        self._stage_event = None              # the newest copy out of it
+        self._word = None                     # pinned: the sort's status word lands here
+        self.rows_uploaded = self.loads = self.groupings = 0
+        self.reset()
+
+    def reset(self):
+        """empty the store (the device buffers are kept)"""
+        self.n_rows = 0
+        self.lengths = []
+        self.marks = np.zeros((0, 3))
+        self._grouped = True                  # the log itself is track after track (a load, an adopted block, nothing at all)
+        self._block = None
+
+    # ---- the two places that touch the device on the way in (a test's stub overrides them) ---------------------------------------------
+    def _reserve(self, n_rows):
+        """room for n_rows rows in all: doubling, a new tensor and one device-to-device copy of the rows held"""
+        import torch
+        if self._log is not None and n_rows <= self.capacity:
+            return
+        while self.capacity < n_rows:
+            self.capacity *= 2
+        log = torch.empty(self.capacity, 14, device=self.device, dtype=torch.float64)
+        tid = torch.empty(self.capacity, device=self.device, dtype=torch.int32)
+        if self._log is not None and self.n_rows:
+            log[:self.n_rows].copy_(self._log[:self.n_rows])
+            tid[:self.n_rows].copy_(self._tid[:self.n_rows])
+        self._log, self._tid = log, tid
+
+    def _upload(self, pieces, ids, at):
+        """pieces: list of [k_i, >= 14] float64 arrays, ids: the track of each piece -> log rows at .. at + sum k_i - 1, through the pinned
+        staging buffer: the rows in one copy, their ids (4 bytes a row) in a second"""
+        import torch
+        k = int(sum(len(p) for p in pieces))
+        if k == 0:
+            return
+        if self._stage_event is not None:
+            self._stage_event.synchronize()      # the copy before this one has left the buffer
+        if self._stage is None or self._stage[0].shape[0] < k:
+            cap = max(k, 2 * (self._stage[0].shape[0] if self._stage is not None else 512))
+            self._stage = (torch.empty(cap, 14, dtype=torch.float64).pin_memory(), torch.empty(cap, dtype=torch.int32).pin_memory())
+        rows, tid = self._stage[0].numpy(), self._stage[1].numpy()
+        o = 0
+        for p, t in zip(pieces, ids):
+            rows[o:o + len(p)] = p[:, :14]
+            tid[o:o + len(p)] = t
+            o += len(p)
+        with torch.cuda.device(self.device):
+            self._log[at:at + k].copy_(self._stage[0][:k], non_blocking=True)
+            self._tid[at:at + k].copy_(self._stage[1][:k], non_blocking=True)
+            self._stage_event = torch.cuda.Event()
+            self._stage_event.record(torch.cuda.current_stream(self.device))
+
+    # ---- bringing the store in step -------------------------------------------------------------------------------------------------------
+    def load(self, tracks):
+        """One upload of all rows, track after track: the log is then grouped as it stands and no kernel is needed.  Returns the rows
+        uploaded, or None -- with the store emptied -- for a list _device_prelude would refuse (a track that is not a float64 array of
+        at least 14 columns, an empty track, more rows or tracks than the sort takes): the caller takes its host path."""
+        tracks = list(tracks)
+        self.reset()
+        lens = [len(t) for t in tracks] if _acceptable(tracks) else None
+        if lens is None or sum(lens) > MAX_ROWS or len(lens) > MAX_TRACKS:
+            return None
+        n = int(sum(lens))
+        self.loads += 1
+        if n:
+            self._reserve(n)
+            self._upload(tracks, range(len(tracks)), 0)
+        self.n_rows, self.lengths = n, lens
+        self.marks = _marks_of(tracks) if tracks else np.zeros((0, 3))
+        self.rows_uploaded += n
+        return n
+
+    def _extends(self, tracks):
+        """True where every stored track is a prefix of the list's track as far as the host can tell without reading rows back, and
+        tracks were only appended: TrackWindows.in_step's test with "the same length" widened to "the same or longer", the marks taken at
+        the rows the store holds"""
+        T = len(self.lengths)
+        if T == 0 or len(tracks) < T or not _acceptable(tracks):
+            return False
+        if any(len(t) < k for t, k in zip(tracks, self.lengths)):
+            return False
+        m = np.empty((T, 3))
+        m[:, 0] = np.fromiter((t[0, 0] for t in tracks[:T]), np.float64, T)
+        m[:, 1] = np.fromiter((t[k - 1, 0] for t, k in zip(tracks, self.lengths)), np.float64, T)
+        m[:, 2] = np.fromiter((t[k - 1, 9] for t, k in zip(tracks, self.lengths)), np.float64, T)
+        return np.array_equal(m, self.marks)
+
+    def sync(self, tracks):
+        """Bring the store in step with a host track list; returns the rows uploaded (None: load's refusal).  Rows and tracks that were
+        only appended go up alone, at the end of the log; anything else -- a track shortened, replaced or edited at its first or last
+        stored row, fewer tracks, an empty store -- is a load."""
+        tracks = list(tracks)
+        if not self._extends(tracks):
+            return self.load(tracks)
+        T = len(self.lengths)
+        pieces, ids = [], []
+        for i, t in enumerate(tracks):
+            k = self.lengths[i] if i < T else 0
+            if len(t) > k:
+                pieces.append(t[k:])
+                ids.append(i)
+        add = int(sum(len(p) for p in pieces))
+        if self.n_rows + add > MAX_ROWS or len(tracks) > MAX_TRACKS:
+            self.reset()
+            return None
+        if add:
+            self._reserve(self.n_rows + add)
+            self._upload(pieces, ids, self.n_rows)
+            self.n_rows += add
+            self.lengths = [len(t) for t in tracks]
+            self.marks = _marks_of(tracks)
+            self.rows_uploaded += add
+            self._grouped = False
+            self._block = None
+        return add
+
+    def adopt(self, block):
+        """merge.merge_packed's block as the new content: its rows are track after track and already on the device, nothing is uploaded.
+        One small copy back: the offsets and the marks of the merged tracks."""
+        import torch
+        rows = block["rows14"]
+        off_d = block["row_offsets"].to(torch.int64)
+        T = int(off_d.shape[0]) - 1
+        self.reset()
+        if T > 0 and rows.shape[0]:
+            first, last = rows.index_select(0, off_d[:-1]), rows.index_select(0, off_d[1:] - 1)
+            small = torch.cat([off_d.to(torch.float64), first[:, 0], last[:, 0], last[:, 9]]).cpu().numpy()
+            off = small[:T + 1].astype(np.int64)
+            self.marks = np.ascontiguousarray(small[T + 1:].reshape(3, T).T)
+        else:
+            off = np.zeros(T + 1, np.int64)
+        self.lengths = np.diff(off).astype(np.int64).tolist()
+        self.n_rows = int(off[-1])
+        self._log = rows[:self.n_rows].contiguous()
+        self.capacity = max(self.n_rows, 1)
+        lens_d = (off_d[1:] - off_d[:-1])
+        self._tid = torch.repeat_interleave(torch.arange(T, device=rows.device, dtype=torch.int32), lens_d, output_size=self.n_rows)
+
+    # ---- handing the rows out ----------------------------------------------------------------------------------------------------------------
+    def packed(self):
+        """{"rows14" [R, 14] float64 on the device, track after track; "row_offsets" [n + 1] int64 numpy; "max_rows"; "n_tracks"; "check"}.
+        Runs the sort and the gather only if rows were appended since the last grouping, and caches the block.  block["check"]() raises
+        OdamError where the sort answered a status: it reads a word whose copy to the host was enqueued HERE, so call it behind a
+        synchronisation the consumer makes anyway (SqFitter.prepare's one small copy) -- it makes none of its own."""
+        import torch
+        if self._block is not None:
+            return self._block
+        T, R = len(self.lengths), self.n_rows
+        off = np.zeros(T + 1, np.int64)
+        off[1:] = np.cumsum(self.lengths)
+        check = lambda: None
+        if R == 0:
+            rows14 = torch.zeros(0, 14, device=self.device, dtype=torch.float64)
+        elif self._grouped:
+            rows14 = self._log[:R]
+        else:
+            with torch.cuda.device(self.device):
+                d_off = torch.from_numpy(off.astype(np.int32)).to(self.device, non_blocking=True)
+                src, status = group(self._tid[:R], T, d_off)
+                rows14 = gather14(self._log[:R], src)
+                if self._word is None:
+                    self._word = torch.zeros(1, dtype=torch.int32).pin_memory()
+                word = self._word
+                word.copy_(status, non_blocking=True)
+            self.groupings += 1
+
+            def check():
+                if int(word[0]) != 0:
+                    raise _lib.OdamError(f"TrackRows: odam_rows_group answered status {int(word[0])} "
+                                         "(1: a track id outside the list, 2: a track whose row count is not the host's)")
+        self._block = {"rows14": rows14, "row_offsets": off, "max_rows": int(max(self.lengths)) if T else 0, "n_tracks": T, "check": check}
+        return self._block

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """per-kernel register / spill / occupancy table of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
-   python tools/kernel_resources.py odam_amd/csrc/conv_gemm.hip [extra hipcc flags]"""
+   python tools/kernel_resources.py odam_amd/csrc/conv_gemm.hip [extra hipcc flags]
+   python tools/kernel_resources.py odam_amd/csrc/track_rows.hip      # the row store's sort and gather: no scratch in any"""
 import re
 import subprocess
 import sys
