@@ -51,7 +51,7 @@ struct ConvGemmArgs {
     // Fused second layer (optional; conv_gemm_big_kernel with pre-split filters, Cout == 64 only): this layer's output
     // tile -- after scale / bias / ReLU -- is not stored but multiplied on chip by a 1x1 layer with F_N = 256 outputs,
     //   F_C[m, n] = act( (relu(C) F_W^T)[m, n] * F_scale[n] + F_bias[n] + F_res[m, n] ),
-    // i.e. a ResNet bottleneck's 3x3 + expand + residual in one launch (detr_model.hip, layer1).  F_Wt3 = the expand
+    // i.e. a ResNet bottleneck's 3x3 + expand + residual in one launch (detr_forward.hip, layer1).  F_Wt3 = the expand
     // filters split by split3_filters(w, 256, 64, .); fp32 only; C is ignored.
     const void* F_Wt3 = nullptr;
     const float* F_scale = nullptr;

@@ -268,7 +268,7 @@ def detr_forward(sd, img, blocks=(3, 4, 6, 3), nheads=8, enc_layers=6, dec_layer
 
 # ---- bf16-faithful mode (BASELINE config 4) ---------------------------------------------------------------------------
 # The same network with every value rounded to bf16 (nearest even) exactly where the gfx950 bf16 mode stores one
-# (odam_amd/csrc/detr_model.hip forward_impl with dtype 1): the image, every weight matrix, every conv / linear output
+# (odam_amd/csrc/detr_forward.hip forward_impl with dtype 1): the image, every weight matrix, every conv / linear output
 # after its fp32 epilogue (x scale + bias (+ residual) (ReLU)), the attention probabilities as the PV operand and the
 # attention output, both LayerNorm outputs (y and y + pos, each rounded from the fp32 value).  Accumulation, FrozenBN
 # scale / bias, biases, softmax (per 64-key tile, running max, exp2 with the scale folded in: attention_bf16_kernel<32>) and
