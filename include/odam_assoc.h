@@ -70,7 +70,8 @@ int odam_assoc_debug_misplace(odam_assoc* m, int on);
  * dims x3, t_wo x3, az_wo, score = columns 0-13 of a track row, layout src/processor.py:98-108); _build writes the
  * associator's track input [T][79][window] float32 for the current camera from them.
  *   _append: n <= 32 observations of one frame; track_ids [host][n] (every id < max_tracks; a new track simply uses the next
- *            id), rows14 [host][n][14].  Within one call every id occurs at most once (a frame adds one observation per track).
+ *            id), rows14 [host][n][14].  Within one call every id occurs at most once (a frame adds one observation per track):
+ *            a call that names a track twice is refused with code 1 before anything is staged or launched; the store is unchanged.
  *   _build:  proj_px [dev][T][4] float64 (odam_sq_project_extents), cam15 [host][15] = rows 0..2 of inv(T_wc) (12), the camera's
  *            azimuth, img_w, img_h; out [dev][T][79][window].
  *   _load:   bulk (re)build -- lengths [host][T] observations per track, rows14 [host][sum_t min(lengths[t], window)][14] = the
@@ -137,7 +138,10 @@ int odam_assoc_hungarian(const float* Z, int n_tracks, int n_det, int ldz, doubl
 int odam_assoc_attach(const float* score, int n_tracks, int n_det, int lds, double match_threshold, double score_threshold, int* match_out,
                       unsigned char* keep_out);
 
-/* log_optimal_transport alone: scores [dev][m, n] with row stride lds, alpha = bin_score */
+/* log_optimal_transport alone: scores [dev][m, n] with row stride lds >= n, alpha = bin_score; Z_out [dev][(m+1), (n+1)], dense.
+ * iters = 0 returns the couplings less the normalisation, Z - norm, from every kernel.  Refused with code 1 before the device is
+ * touched: m or n < 1, lds < n, iters < 0, and a shape whose kernel would need more than the 150 KB of LDS the library enables
+ * (n <= 31 and m <= 1099: (m+1) * 34 + 32 floats; else (m+1) * (n+1) + (m+1) + (n+1) floats; the text names need and limit). */
 int odam_assoc_sinkhorn(const float* scores, int lds, int m, int n, float alpha, int iters, float* Z_out, void* stream);
 
 #ifdef __cplusplus

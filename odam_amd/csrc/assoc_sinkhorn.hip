@@ -248,7 +248,7 @@ __global__ __launch_bounds__(64) void sinkhorn_wave_kernel(const float* __restri
         bool good = true;
 #pragma unroll
         for (int j = 0; j < RB; j++) {
-            u[j] = mu[j] != 0.0f ? -rho[j] : 0.0f;
+            u[j] = (mu[j] != 0.0f && iters > 0) ? -rho[j] : 0.0f;      // no iteration, no absorption: the result is Z - norm, as from every other kernel
             a[j] = 0.0f;
 #pragma unroll
             for (int c = 0; c < NC; c++) K[j][c] = expf(z[j][c] + u[j]);          // exp(-inf) = 0 outside the matrix
@@ -352,35 +352,50 @@ __global__ __launch_bounds__(64) void sinkhorn_wave_kernel(const float* __restri
 
 // The two LDS-resident kernels hold up to 150 KB of dynamic LDS (the default bound is 64 KB): allowed here, once per device, before
 // their first launch from either entry point
+constexpr size_t SK_LDS_MAX = 150 * 1024;
 int allow_big_lds() {
     static bool done[64] = {};
     int dev = 0;
     ODAM_HIP(hipGetDevice(&dev));
     if (done[dev & 63]) return 0;
-    ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_MAX));
+    ODAM_HIP(hipFuncSetAttribute((const void*)sinkhorn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_MAX));
     done[dev & 63] = true;
     return 0;
+}
+
+// which of the three kernels launch_sinkhorn takes for m rows and room for n_cap columns (dustbins not counted), and the dynamic LDS it asks for
+enum SkKernel { SK_WAVE, SK_COLS32, SK_GENERAL };
+SkKernel sinkhorn_choice(size_t m, size_t n_cap, size_t* lds_bytes) {
+    if (n_cap + 1 <= 32 && m + 1 <= 128 && odam_cfg::get(odam_cfg::ASSOC_SK_FAST) != 0) { *lds_bytes = 0; return SK_WAVE; }      // one wavefront, registers only
+    if (n_cap + 1 <= 32 && m + 1 <= 1100) { *lds_bytes = ((m + 1) * 33 + (m + 1) + 32) * sizeof(float); return SK_COLS32; }      // 1100 rows of 33 floats + u + v fit the 150 KB
+    *lds_bytes = ((m + 1) * (n_cap + 1) + (m + 1) + (n_cap + 1)) * sizeof(float);
+    return SK_GENERAL;
 }
 
 }  // namespace
 
 int odam_assoc_internal::launch_sinkhorn(const float* scores, int lds_, int m_, int n_, int n_cap, float alpha, int iters, float* Z_out,
                                          const int* n_dev, hipStream_t st, const unsigned* err, unsigned* lost_count, bool* cleans_bar) {
-    if (n_cap + 1 <= 32 && m_ + 1 <= 128 && odam_cfg::get(odam_cfg::ASSOC_SK_FAST) != 0) {       // one wavefront, registers only
+    size_t lds = 0;
+    const SkKernel which = sinkhorn_choice((size_t)m_, (size_t)n_cap, &lds);
+    if (lds > SK_LDS_MAX) {
+        char msg[200];
+        std::snprintf(msg, sizeof(msg), "launch_sinkhorn: %d x %d needs %zu bytes of LDS, the limit is %zu (the (m+1) x (n+1) matrix, u and v)", m_, n_cap, lds, SK_LDS_MAX);
+        return odam_fail(1, msg);
+    }
+    if (which == SK_WAVE) {
         const int nc = (n_cap + 1 + 7) >> 3;
 #define ODAM_SKW(RB, NC) hipLaunchKernelGGL((sinkhorn_wave_kernel<RB, NC>), dim3(1), dim3(64), 0, st, scores, lds_, m_, n_, alpha, iters, Z_out, n_dev, err, lost_count, odam_cfg::get(odam_cfg::ASSOC_SK_FAST) - 1)
         if (m_ + 1 <= 64) { if (nc == 1) ODAM_SKW(1, 8); else if (nc == 2) ODAM_SKW(1, 16); else if (nc == 3) ODAM_SKW(1, 24); else ODAM_SKW(1, 32); }
         else { if (nc == 1) ODAM_SKW(2, 8); else if (nc == 2) ODAM_SKW(2, 16); else if (nc == 3) ODAM_SKW(2, 24); else ODAM_SKW(2, 32); }
 #undef ODAM_SKW
         if (cleans_bar) *cleans_bar = err != nullptr;
-    } else if (n_cap + 1 <= 32 && m_ + 1 <= 1100) {        // 1100 rows of 33 floats + u + v fit the 150 KB of dynamic LDS
+    } else if (which == SK_COLS32) {
         if (int rc = allow_big_lds()) return rc;
-        const size_t lds = ((size_t)(m_ + 1) * 33 + (m_ + 1) + 32) * sizeof(float);
         hipLaunchKernelGGL(sinkhorn32_kernel, dim3(1), dim3(SK_NT), lds, st, scores, lds_, m_, n_, alpha, iters, Z_out, n_dev, err, lost_count);
     } else {
         if (int rc = allow_big_lds()) return rc;
-        const size_t lds = ((size_t)(m_ + 1) * (n_cap + 1) + (m_ + 1) + (n_cap + 1)) * sizeof(float);
         hipLaunchKernelGGL(sinkhorn_kernel, dim3(1), dim3(SK_NT), lds, st, scores, lds_, m_, n_, alpha, iters, Z_out, n_dev, err, lost_count);
     }
     ODAM_HIP(hipGetLastError());
@@ -389,7 +404,16 @@ int odam_assoc_internal::launch_sinkhorn(const float* scores, int lds_, int m_, 
 
 extern "C" int odam_assoc_sinkhorn(const float* scores, int lds_, int m_, int n_, float alpha, int iters, float* Z_out,
                                    void* stream) {
-    if (!scores || !Z_out || m_ < 1 || n_ < 1 || (size_t)(m_ + 1) * (n_ + 1) > 36000)
-        return odam_fail(1, "odam_assoc_sinkhorn: bad argument");
+    if (!scores || !Z_out || m_ < 1 || n_ < 1) return odam_fail(1, "odam_assoc_sinkhorn: bad argument");
+    if (lds_ < n_) return odam_fail(1, "odam_assoc_sinkhorn: row stride lds must be at least n");
+    if (iters < 0) return odam_fail(1, "odam_assoc_sinkhorn: iters must be at least 0");
+    // the whole matrix lives in one workgroup's LDS (or one wavefront's registers): what the kernel launch_sinkhorn would take needs
+    size_t need = ~(size_t)0;
+    if ((size_t)m_ <= SK_LDS_MAX && (size_t)n_ <= SK_LDS_MAX) (void)sinkhorn_choice((size_t)m_, (size_t)n_, &need);      // (beyond that u or v alone do not fit; no overflow below it)
+    if (need > SK_LDS_MAX) {
+        char msg[200];
+        std::snprintf(msg, sizeof(msg), "odam_assoc_sinkhorn: %d x %d needs %zu bytes of LDS, the limit is %zu (the (m+1) x (n+1) matrix, u and v)", m_, n_, need, SK_LDS_MAX);
+        return odam_fail(1, msg);
+    }
     return odam_assoc_internal::launch_sinkhorn(scores, lds_, m_, n_, n_, alpha, iters, Z_out, nullptr, (hipStream_t)stream);
 }

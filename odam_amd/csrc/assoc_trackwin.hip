@@ -166,6 +166,10 @@ extern "C" int odam_trackwin_append(odam_trackwin* w, int n, const int* track_id
     hipStream_t st = (hipStream_t)stream;
     for (int i = 0; i < n; i++)
         if (track_ids[i] < 0 || track_ids[i] >= w->max_tracks) return odam_fail(3, "odam_trackwin_append: track id outside the handle's capacity");
+    // the kernel takes one block per observation and reads the track's count once: two rows of one track in one call would land in the same ring slot
+    for (int i = 1; i < n; i++)
+        for (int j = 0; j < i; j++)
+            if (track_ids[i] == track_ids[j]) return odam_fail(1, "odam_trackwin_append: a track is named twice in one call (one observation per track and call)");
     // The ring slot may be rewritten only once the kernel that read it eight appends ago has run -- appends can queue behind long
     // kernels on the stream (a detector forward, a rebuild).
     const int si = (int)(w->slot++ & 7);

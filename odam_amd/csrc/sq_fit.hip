@@ -1236,7 +1236,7 @@ __global__ __launch_bounds__(256) void project_extent_kernel(const float* __rest
 
 extern "C" int odam_sq_project_extents(odam_sq_ctx* ctx, int n, const float* params, const double* T_cw12_K9, double* out_px,
                                        void* stream) {
-    if (!ctx || !params || !T_cw12_K9 || !out_px || n < 0) return odam_fail(ODAM_E_INVALID, "odam_sq_project_extents: bad arguments");
+    if (!ctx || n < 0 || (n && (!params || !T_cw12_K9 || !out_px))) return odam_fail(ODAM_E_INVALID, "odam_sq_project_extents: bad arguments");      // (no tracks: empty arrays have null pointers)
     if (n == 0) return ODAM_OK;
     hipStream_t st = (hipStream_t)stream;
     if ((size_t)n > ctx->proj_pts_n) {

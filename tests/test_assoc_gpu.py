@@ -71,6 +71,91 @@ def test_sinkhorn_rows_on_lanes_vs_float64(m, n, scale):
         assert (np.abs(np.exp(o) - np.exp(ref)) / np.maximum(np.exp(ref), 1.0)).max() <= 2 * tol      # entries are probabilities x (m + n)
 
 
+def _sinkhorn_f32(sc, alpha, iters):
+    """the same iteration as the reference runs it: float32 torch on the CPU, torch.logsumexp (associator.py:283-312) -> float64 array"""
+    sc = torch.from_numpy(np.asarray(sc, np.float32))
+    m, n = sc.shape
+    Z = torch.full((m + 1, n + 1), float(alpha), dtype=torch.float32); Z[:m, :n] = sc
+    ms, ns = torch.tensor(float(m)), torch.tensor(float(n))
+    norm = -(ms + ns).log()
+    log_mu = torch.cat([norm.expand(m), ns.log()[None] + norm]); log_nu = torch.cat([norm.expand(n), ms.log()[None] + norm])
+    u, v = torch.zeros_like(log_mu), torch.zeros_like(log_nu)
+    for _ in range(iters):
+        u = log_mu - torch.logsumexp(Z + v[None, :], 1)
+        v = log_nu - torch.logsumexp(Z + u[:, None], 0)
+    return (Z + u[:, None] + v[None, :] - norm).double().numpy()
+
+
+def _sinkhorn_kernels(m, n):
+    """[(assoc.sk_fast setting, kernel name)] of every setting launch_sinkhorn honours for an m x n problem (csrc/assoc_sinkhorn.hip): the
+    one-wavefront kernel's three rungs up to 128 x 32 incl. the dustbins, and what it takes with assoc.sk_fast = 0 or beyond that size"""
+    big = "cols32" if n + 1 <= 32 and m + 1 <= 1100 else "general"
+    if n + 1 <= 32 and m + 1 <= 128:
+        return [(1, "wave_absorb10"), (2, "wave_absorb1"), (3, "wave_log"), (0, big)]
+    return [(1, big)]
+
+
+def _sinkhorn_device(sc, alpha, iters, pad, fast):
+    """odam_assoc_sinkhorn on scores [m, n] stored with row stride n + pad (NaN in the padding) under assoc.sk_fast = fast"""
+    from odam_amd import _lib
+    m, n = sc.shape
+    d = torch.full((m, n + pad), float("nan"), device=DEV)
+    d[:, :n] = torch.from_numpy(sc).to(DEV)
+    out = torch.full(((m + 1) * (n + 1) + 64,), -12345.0, device=DEV)
+    _lib.set_config("assoc.sk_fast", fast)
+    try:
+        _lib.check(_lib.lib().odam_assoc_sinkhorn(_lib.ptr(d), n + pad, m, n, ctypes.c_float(alpha), iters, _lib.ptr(out),
+                                                  ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)), "sinkhorn")
+        o = out.cpu().numpy()
+    finally:
+        _lib.set_config("assoc.sk_fast", 1)
+    assert (o[(m + 1) * (n + 1):] == -12345.0).all()                 # nothing written past the dense (m + 1) x (n + 1) result
+    return o[:(m + 1) * (n + 1)].reshape(m + 1, n + 1).astype(np.float64)
+
+
+# (m, n, scale of the scores, alpha = dustbin score, iterations, padding of the row stride)
+_SK_CASES = (
+    # the general 1024-thread kernel: more than 32 columns incl. the dustbin, or more than 1100 rows; 1100 x 31 is the first row count past the
+    # 32-column kernel and 1099 x 31 the last one inside it; 1127 x 32 is the largest 33-column problem the enabled LDS holds
+    [(40, 40, 3.0, 1.0, 100, 0), (5, 200, 8.0, 1.0, 100, 0), (200, 33, 8.0, 1.0, 100, 0), (1, 300, 3.0, 1.0, 100, 0), (33, 32, 20.0, 1.0, 100, 0),
+     (1100, 31, 8.0, 1.0, 100, 0), (1099, 31, 8.0, 1.0, 100, 0), (1127, 32, 8.0, 1.0, 100, 0)]
+    # iteration counts around the absorb-every-10 cadence of the one-wavefront kernel: none, fewer than a period, one period, remainders
+    + [(m, 30, s, 1.0, it, 0) for m, s in ((63, 8.0), (127, 20.0)) for it in (0, 1, 7, 10, 11, 25)]
+    # dustbin scores
+    + [(m, n, 8.0, a, 100, 0) for a in (-7.0, 0.0, 4.0, 12.0) for m, n in ((63, 30), (200, 33), (300, 30))]
+    + [(63, 30, 8.0, 12.0, 0, 0), (64, 31, 4.0, -7.0, 1, 0), (5, 200, 8.0, -7.0, 0, 0), (200, 33, 8.0, 4.0, 25, 0), (1, 300, 3.0, 0.0, 7, 0), (33, 32, 20.0, 1.0, 11, 0)]
+    # a row stride larger than n, NaN between the rows
+    + [(63, 30, 8.0, 1.0, 100, 3), (127, 30, 20.0, 4.0, 11, 3), (40, 40, 3.0, 1.0, 100, 3), (300, 30, 8.0, -7.0, 100, 3), (1, 300, 3.0, 1.0, 100, 3),
+       (63, 30, 8.0, 12.0, 0, 3)])
+
+
+@pytest.mark.parametrize("m,n,scale,alpha,iters,pad", _SK_CASES, ids=["%dx%d-s%g-a%g-it%d-pad%d" % c for c in _SK_CASES])
+def test_sinkhorn_every_kernel_iteration_count_dustbin_score_and_stride(m, n, scale, alpha, iters, pad, measured):
+    """odam_assoc_sinkhorn on every kernel behind launch_sinkhorn -- the general 1024-thread kernel had no test: every other case has at most 31
+    columns and 300 rows -- for iteration counts other than 100 (0 returns Z - norm: the one-wavefront kernel used to return Z - rowmax - norm),
+    dustbin scores other than 1 and a row stride larger than n, against the float64 iteration within the file's tolerance
+    2e-5 * max(1, |ref|max).  Recorded: the error relative to that of the reference's own float32 arithmetic (torch.logsumexp on the CPU)."""
+    rng = np.random.default_rng(m * 1000 + n)
+    sc = (rng.standard_normal((m, n)) * scale).astype(np.float32)
+    if (m + n) % 3 == 0:
+        sc += 100.0
+    ref = _sinkhorn_f64(sc.astype(np.float64), alpha, iters)
+    assert np.isfinite(ref).all()
+    tol = 2e-5 * max(1.0, float(np.abs(ref).max()))
+    f32_err = float(np.abs(_sinkhorn_f32(sc, alpha, iters) - ref).max())
+    floor = 2.0 ** -24 * max(1.0, float(np.abs(ref).max()))          # half an ulp of the largest entry: the ratio's denominator where float32 happens to be exact
+    results = []
+    for fast, kernel in _sinkhorn_kernels(m, n):
+        o = _sinkhorn_device(sc, alpha, iters, pad, fast)
+        err = float(np.abs(o - ref).max()) if np.isfinite(o).all() else float("inf")
+        print("sinkhorn %-13s %4d x %3d scale %g alpha %g iters %3d pad %d  err %.3e  float32 reference %.3e  tolerance %.3e"
+              % (kernel, m, n, scale, alpha, iters, pad, err, f32_err, tol))
+        measured("sinkhorn.%s.%dx%d.a%g.it%d.pad%d" % (kernel, m, n, alpha, iters, pad), err / max(f32_err, floor))
+        results.append((kernel, err))
+    for kernel, err in results:
+        assert err <= tol, (kernel, err, tol)
+
+
 @pytest.mark.parametrize("merge", [1, 0], ids=["merge projection folded into the MLP", "merge projection as its own layer"])
 def test_forward_vs_reference_associator(golden, merge):
     """the association forward against the reference's own (src/models/associator.py:202-254 run on the CPU, tests/golden/assoc.npz), in both
@@ -676,6 +761,72 @@ def _hungarian_device(scores_or_Z, thr, log_domain):
     return o[:n].astype(np.float64), int(o[31])
 
 
+def _hungarian_device_ld(M, thr, log_domain, pad=0):
+    """_hungarian_device for any size the entry accepts: M [T, n] stored with row stride n + pad (NaN in the padding), match_out of n entries
+    inside a larger buffer whose other words must come back untouched -> match [n], status"""
+    from odam_amd import _lib
+    M = np.asarray(M, np.float32)
+    T, n = M.shape
+    buf = torch.full((max(T, 1), max(n + pad, 1)), float("nan"), device=DEV)      # (an empty matrix still needs a pointer)
+    if T and n:
+        buf[:T, :n] = torch.from_numpy(M).to(DEV)
+    out = torch.full((n + 8,), -7, dtype=torch.int32, device=DEV)
+    _lib.check(_lib.lib().odam_assoc_hungarian(_lib.ptr(buf), ctypes.c_int(T), ctypes.c_int(n), ctypes.c_int(n + pad), ctypes.c_double(thr),
+                                               ctypes.c_int(log_domain), _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * (n + 7)),
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "odam_assoc_hungarian")
+    torch.cuda.synchronize()
+    o = out.cpu().numpy()
+    assert (o[n:n + 7] == -7).all()
+    return o[:n].astype(np.float64), int(o[n + 7])
+
+
+def _hungarian_at_its_limits():
+    """(the second half of test_hungarian_on_the_device_equals_scipy)  hungarian_wave_kernel where its layout ends: 32 rows after the solver's transposition (the last row index the tie key's 5 bits hold) and
+    128 columns (both columns of every lane), tall, wide and square; random scores, a constant matrix and a three-valued one (scipy's tie order
+    is part of the result), thresholds 0 and 0.2, scores given directly and as logarithms, a row stride larger than n_det with NaN between the
+    rows; problems without tracks or without detections."""
+    from odam_amd.associator import hungarian_matching
+    rng = np.random.default_rng(17)
+    n_run = 0
+    for T, n in ((128, 32), (32, 128), (32, 32), (31, 128)):
+        three = rng.integers(0, 3, (T, n))
+        linear = [rng.random((T, n), dtype=np.float32), np.full((T, n), 0.5, np.float32), (three / 4).astype(np.float32)]
+        # as logarithms: the scores are exp() of the device there and of torch on the host, an ulp apart at most -- the tie matrices are made
+        # of values whose cost 1 - exp(z) does not feel an ulp: exp(-inf) = 0, exp(0) = 1, and exp(-20) = 2e-9 (cost 1.0f, score above a
+        # threshold of 0)
+        logs = [np.log(linear[0]), np.zeros((T, n), np.float32), np.array([-np.inf, 0.0, -20.0], np.float32)[three]]
+        for log_domain, mats in ((0, linear), (1, logs)):
+            for M in mats:
+                sc = torch.from_numpy(M).exp() if log_domain else torch.from_numpy(M)
+                for thr in (0.0, 0.2):
+                    want = hungarian_matching(sc, thr)
+                    for pad in (0, 5):
+                        got, st = _hungarian_device_ld(M, thr, log_domain, pad)
+                        assert st == 0 and np.array_equal(got, want), (T, n, log_domain, thr, pad, got, want)
+                        n_run += 1
+                assert (want >= 0).sum() >= min(T, n) // 4      # (not a matrix that matches nothing)
+    assert n_run == 4 * 6 * 4
+    # the existing helper's sizes through the new one: same answers with a padded stride
+    for T, n in ((5, 3), (3, 5), (17, 30), (100, 30)):
+        M = rng.random((T, n), dtype=np.float32)
+        want = hungarian_matching(torch.from_numpy(M), 0.2)
+        for pad in (0, 5):
+            got, st = _hungarian_device_ld(M, 0.2, 0, pad)
+            assert st == 0 and np.array_equal(got, want), (T, n, pad)
+    # no tracks, no detections, neither: every detection unmatched, status 0
+    for T, n in ((0, 7), (0, 128), (9, 0), (0, 0)):
+        for log_domain in (0, 1):
+            got, st = _hungarian_device_ld(np.zeros((T, n), np.float32), 0.1, log_domain, 5)
+            assert st == 0 and got.shape == (n,) and (got == -1).all(), (T, n)
+    # one past either limit: refused with ODAM_E_LIMIT (3), the caller solves on the host
+    from odam_amd import _lib
+    out = torch.zeros(160, dtype=torch.int32, device=DEV)
+    for T, n in ((33, 128), (32, 129), (128, 33), (129, 32)):
+        big = torch.rand(T, n, device=DEV)
+        assert _lib.lib().odam_assoc_hungarian(_lib.ptr(big), T, n, n, ctypes.c_double(0.1), 0, _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * 159),
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 3
+
+
 def test_hungarian_on_the_device_equals_scipy():
     """odam_assoc_hungarian (scipy's rectangular shortest-augmenting-path solver restated on one wavefront, associator.py:19-35) against
     hungarian_matching = scipy.optimize.linear_sum_assignment on the same float32 scores: random matrices wide, tall and square up to
@@ -721,4 +872,5 @@ def test_hungarian_on_the_device_equals_scipy():
                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 3
     _, st = _hungarian_device(np.full((4, 3), np.nan, np.float32), 0.1, 0)
     assert st == 1
+    _hungarian_at_its_limits()
 
