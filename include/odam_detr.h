@@ -281,7 +281,44 @@ int odam_op_conv2d_nhwc_mxfp8(const void* x, const void* xs, const void* w_packe
                               const float* bias, const void* residual, void* y, void* ys, void* y_bf16, float* y_f32,
                               int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
                               int Kpad, int relu, int k_order, void* stream);
+/* ---- the kernels between the contractions, one launch each through the launcher the forward calls (tests/test_detr_elementwise_gpu.py
+ * holds each to an exact or float64 reference).  Every entry checks its arguments before any HIP call -- null pointers, dtype 0 (fp32)
+ * / 1 (bf16), negative extents and what is noted per entry -- and returns 1 (ODAM_E_INVALID) with its name in odam_last_error(); an
+ * extent of 0 is a successful call that launches nothing.  bf16 tensors are raw bfloat16 (the upper 16 bits of the float32), written
+ * with round-to-nearest-even. */
+/* torchvision's stem pool, nn.MaxPool2d(3, stride 2, padding 1), on NHWC: x [dev][B,H,W,C] -> y [dev][B,Ho,Wo,C], Ho = (H - 1) / 2 + 1,
+ * Wo = (W - 1) / 2 + 1, x and y of `dtype`, C % 4 == 0.  A window tap outside the image counts as -inf, so an all-negative window
+ * gives its (negative) maximum and -inf inputs pass through; the result is one of the inputs, bit for bit.  NaN inputs are outside the
+ * contract: the kernel takes fmaxf, which drops a NaN where torch.nn.functional.max_pool2d propagates it. */
+int odam_op_maxpool3x3s2_nhwc_ex(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+/* the same for fp32 tensors (= _ex with dtype 0) */
 int odam_op_maxpool3x3s2_nhwc(const float* x, float* y, int B, int H, int W, int C, void* stream);
+/* The network input into the stem's layout: in [dev][B,3,H,W] float32 (NCHW) -> pixel-major out of `dtype`, every element of it written.
+ *   framed == 0, dtype 0:  out [B][H][W][4] float32        -- channels 0-2 the image, channel 3 = +0.0
+ *   framed == 0, dtype 1:  out [B][H][W][8] bf16           -- one 16-byte chunk per pixel: 3 real channels and 5 of +0.0
+ *   framed != 0:           out [B][H + 6][W + 8][4] of `dtype` (4 channels in bf16 too) -- the picture at rows 3 .. H + 2, columns
+ *                          3 .. W + 2 (pixel (y, x) at [y + 3][x + 3]), channel 3 = +0.0, and every pixel of the frame (3 rows above
+ *                          and below, 3 columns left, 5 right) +0.0: what the stem as a 7x1 convolution over 8-pixel rows reads.  The
+ *                          frame is written by every call, never left over from the call before.
+ * bf16 values are the float32 inputs rounded to nearest even. */
+int odam_op_nchw_to_nhwc4(const float* in, void* out, int B, int H, int W, int dtype, int framed, void* stream);
+/* in [dev][B,H,W,C] of `dtype` (NHWC, any C >= 0) -> out [dev][B,C,H,W] float32 (NCHW); values unchanged (bf16 widened exactly) */
+int odam_op_nhwc_to_nchw(const void* in, float* out, int B, int H, int W, int C, int dtype, void* stream);
+/* out[row][c] = x[row][c] + pos[row % L][c] (x null: out[row][c] = pos[row % L][c]) for row < M: x (nullable), out [dev][M][C] of
+ * `dtype`, pos [dev][L][C] float32, C % 4 == 0, L > 0.  One float32 addition, then for bf16 one rounding to nearest even.  C == 256 runs
+ * the kernel the shipped width uses, any other C the general one. */
+int odam_op_add_pos(const void* x, const float* pos, int L, void* out, int M, int C, int dtype, void* stream);
+/* in [dev][n] of `dtype` -> out [dev][n] float32, exactly (dtype 0: a copy).  n % 4 == 0, else code 1 and nothing is written. */
+int odam_op_to_f32(const void* in, float* out, long long n, int dtype, void* stream);
+/* x[i] = 1 / (1 + expf(-x[i])) in place, x [dev][n] float32 (the box head's sigmoid, detr.py:76) */
+int odam_op_sigmoid(float* x, int n, void* stream);
+/* odam_detr_postprocess without a model handle: n queries (any batch flattened), n_cls1 >= 2 logits per query (the last one "no
+ * object"), n_bins >= 1 angle logits; logits [dev][n][n_cls1], boxes [n][4] (cx, cy, w, h in 0 .. 1), angle [n][n_bins], offset [n][2],
+ * size [n][3], depth [n], K9 [host] row-major 3x3 intrinsics -> rows [dev][n][16] as odam_detr_postprocess writes them: the score is the
+ * largest softmax probability among the first n_cls1 - 1 classes, class and angle bin the FIRST index of the maximum. */
+int odam_op_postprocess(const float* logits, const float* boxes, const float* angle, const float* offset, const float* size,
+                        const float* depth, int n, int n_cls1, int n_bins, const float* K9, float img_w, float img_h, float* rows,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -953,6 +953,7 @@ __global__ __launch_bounds__(256) void to_f32_kernel(const T* __restrict__ in, f
 }
 
 int launch_to_f32(const void* in, float* out, size_t n, int dtype, hipStream_t stream) {
+    if (n % 4) return odam_fail(1, "launch_to_f32: n must be a multiple of 4");      // whole float4 groups: no tail is dropped
     const size_t n4 = n / 4;
     if (!n4) return 0;
 #define ODAM_K(T, ...) hipLaunchKernelGGL(to_f32_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const T*)in, out, n4)

@@ -1,5 +1,5 @@
 // detr_ops.hip -- single-operator entry points of include/odam_detr.h: what tests and tools call to drive one kernel of the
-// detector -- a convolution, an attention, a LayerNorm -- through the launchers the forward uses.  Each family of entries
+// detector -- a convolution, an attention, a LayerNorm, a pooling / layout / elementwise pass -- through the launchers the forward uses.  Each family of entries
 // shares one checked implementation; which checks an entry runs, and the name its error texts begin with, are its own.
 #include <hip/hip_runtime.h>
 
@@ -116,6 +116,16 @@ int layernorm_op(const char* who, bool checked, const void* x, const void* r, co
         if (C % 64 || C < 128 || C > 1024) return fail(1, who, "C must be a multiple of 64 in 128 .. 1024");
     }
     return odam_dk::launch_add_layernorm(x, r, gamma, beta, y, pos, y_pos ? L : 1, y_pos, M, dtype, (hipStream_t)stream, C);
+}
+
+// ---- 3x3 / stride 2 / pad 1 max-pool: odam_op_maxpool3x3s2_nhwc (fp32) and _ex ----
+int maxpool_op(const char* who, const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream) {
+    if (!x || !y) return fail(1, who, "null pointer");
+    if (dtype != 0 && dtype != 1) return fail(1, who, "dtype must be 0 (fp32) or 1 (bf16)");
+    if (B < 0 || H < 0 || W < 0 || C < 0) return fail(1, who, "negative extent");
+    if (C % 4) return fail(1, who, "C must be a multiple of 4");
+    if (!B || !H || !W || !C) return 0;
+    return odam_dk::launch_maxpool3x3s2(x, y, B, H, W, C, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), dtype, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -271,8 +281,69 @@ extern "C" int odam_op_add_layernorm_c(const void* x, const void* r, const float
     return layernorm_op("odam_op_add_layernorm_c", true, x, r, gamma, beta, y, pos, L, y_pos, M, C, dtype, stream);
 }
 
+// ---- the kernels between the contractions: pooling, layouts, position add, convert, sigmoid, post-processing.  Every entry
+// checks its arguments before any HIP call and then calls the launcher the forward calls ----
+extern "C" int odam_op_maxpool3x3s2_nhwc_ex(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream) {
+    return maxpool_op("odam_op_maxpool3x3s2_nhwc_ex", x, y, B, H, W, C, dtype, stream);
+}
+
 extern "C" int odam_op_maxpool3x3s2_nhwc(const float* x, float* y, int B, int H, int W, int C, void* stream) {
-    if (!x || !y || C % 4) return odam_fail(1, "odam_op_maxpool3x3s2_nhwc: bad argument");
-    return odam_dk::launch_maxpool3x3s2(x, y, B, H, W, C, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), 0,
-                                        (hipStream_t)stream);
+    return maxpool_op("odam_op_maxpool3x3s2_nhwc", x, y, B, H, W, C, 0, stream);
+}
+
+extern "C" int odam_op_nchw_to_nhwc4(const float* in, void* out, int B, int H, int W, int dtype, int framed, void* stream) {
+    const char* who = "odam_op_nchw_to_nhwc4";
+    if (!in || !out) return fail(1, who, "null pointer");
+    if (dtype != 0 && dtype != 1) return fail(1, who, "dtype must be 0 (fp32) or 1 (bf16)");
+    if (B < 0 || H < 0 || W < 0) return fail(1, who, "negative extent");
+    if (!B || !H || !W) return 0;
+    return framed ? odam_dk::launch_nchw_to_nhwc4_framed(in, out, B, H, W, dtype, (hipStream_t)stream)
+                  : odam_dk::launch_nchw_to_nhwc4(in, out, B, H, W, dtype, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_nhwc_to_nchw(const void* in, float* out, int B, int H, int W, int C, int dtype, void* stream) {
+    const char* who = "odam_op_nhwc_to_nchw";
+    if (!in || !out) return fail(1, who, "null pointer");
+    if (dtype != 0 && dtype != 1) return fail(1, who, "dtype must be 0 (fp32) or 1 (bf16)");
+    if (B < 0 || H < 0 || W < 0 || C < 0) return fail(1, who, "negative extent");
+    return odam_dk::launch_nhwc_to_nchw(in, out, B, H, W, C, dtype, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_add_pos(const void* x, const float* pos, int L, void* out, int M, int C, int dtype, void* stream) {
+    const char* who = "odam_op_add_pos";
+    if (!pos || !out) return fail(1, who, "null pointer");
+    if (dtype != 0 && dtype != 1) return fail(1, who, "dtype must be 0 (fp32) or 1 (bf16)");
+    if (M < 0 || C < 0) return fail(1, who, "negative extent");
+    if (C % 4) return fail(1, who, "C must be a multiple of 4");
+    if (L <= 0) return fail(1, who, "L must be positive");
+    if (!M || !C) return 0;
+    return odam_dk::launch_add_pos(x, pos, L, out, M, dtype, (hipStream_t)stream, C);
+}
+
+extern "C" int odam_op_to_f32(const void* in, float* out, long long n, int dtype, void* stream) {
+    const char* who = "odam_op_to_f32";
+    if (!in || !out) return fail(1, who, "null pointer");
+    if (dtype != 0 && dtype != 1) return fail(1, who, "dtype must be 0 (fp32) or 1 (bf16)");
+    if (n < 0) return fail(1, who, "negative extent");
+    if (n % 4) return fail(1, who, "n must be a multiple of 4");
+    return odam_dk::launch_to_f32(in, out, (size_t)n, dtype, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_sigmoid(float* x, int n, void* stream) {
+    if (!x) return fail(1, "odam_op_sigmoid", "null pointer");
+    if (n < 0) return fail(1, "odam_op_sigmoid", "negative extent");
+    return odam_dk::launch_sigmoid(x, n, (hipStream_t)stream);
+}
+
+extern "C" int odam_op_postprocess(const float* logits, const float* boxes, const float* angle, const float* offset, const float* size,
+                                   const float* depth, int n, int n_cls1, int n_bins, const float* K9, float img_w, float img_h,
+                                   float* rows, void* stream) {
+    const char* who = "odam_op_postprocess";
+    if (!logits || !boxes || !angle || !offset || !size || !depth || !K9 || !rows) return fail(1, who, "null pointer");
+    if (n < 0) return fail(1, who, "negative extent");
+    if (n_cls1 < 2) return fail(1, who, "n_cls1 must be at least 2 (one class and no-object)");
+    if (n_bins < 1) return fail(1, who, "n_bins must be at least 1");
+    if (!n) return 0;
+    return odam_dk::launch_postprocess(logits, boxes, angle, offset, size, depth, 1, n, n_cls1, n_bins, img_w, img_h, K9[0], K9[4],
+                                       K9[2], K9[5], rows, (hipStream_t)stream);
 }

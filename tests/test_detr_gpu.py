@@ -412,11 +412,25 @@ def test_streamed_detection_equals_plain_forward(model):
     assert np.allclose(det.detect_resident(frames, (640, 480), K), plain, rtol=0, atol=2e-6)
 
 
+def _transform_diff(got, host):
+    d = got != host
+    step = (got - host).abs().max().item() * 255 * 0.225          # in units of one 8-bit level of the resized image (largest std)
+    return f"device transform: {int(d.sum())} of {d.numel()} values differ from the host transform, by up to {step:.2f} 8-bit levels"
+
+
 @pytest.mark.parametrize("w,h,resize", [(640, 480, (800, 1333)), (800, 600, (800, 1333)), (96, 72, (240, 400)),
-                                        (57, 131, (120, 200)), (400, 300, (150, 1333)), (321, 240, (240, 1333))])
+                                        (57, 131, (120, 200)), (400, 300, (150, 1333)), (321, 240, (240, 1333)),
+                                        (64, 48, (48, 1333)),           # already at the target size: neither pass runs
+                                        (40, 1, (32, 1333)),            # one source row -> 32 x 1280
+                                        (1, 40, (32, 1333)),            # one source column -> 1280 x 32
+                                        (2, 2, (64, 1333)),             # 2 x 2 up-scaled to 64 x 64
+                                        (400, 300, (33, 1333)),         # down-scale by 9.09: 19 + 19 taps per output pixel
+                                        (510, 64, (32, 1333)), (512, 64, (32, 1333)), (514, 64, (32, 1333)),      # output widths 255, 256, 257:
+                                        (1026, 64, (32, 1333))])                                                  # ... and 513, around the 256-pixel blocks
 def test_device_transform_equals_host_transform(model, w, h, resize):
     """A1 on the device (PIL bilinear resize in 22-bit fixed point, /255, normalise) is bit-identical to the PIL +
-    torch host transform, for up-scaling, down-scaling and a pass-through axis"""
+    torch host transform, for up-scaling, down-scaling, a pass-through axis or two, extents of 1 and 2, and output widths on
+    either side of the kernel's 256-pixel blocks"""
     from odam_amd import transforms
     det, _ = model
     rng = np.random.default_rng(w * 1000 + h)
@@ -430,7 +444,35 @@ def test_device_transform_equals_host_transform(model, w, h, resize):
     finally:
         det.resize = (800, 1333)
     assert got.shape == host.shape
-    assert torch.equal(got, host)
+    assert torch.equal(got, host), _transform_diff(got, host)
+
+
+@pytest.mark.parametrize("w,h,resize,out_hw", [(96, 72, (240, 400), (240, 320)), (400, 300, (33, 1333), (33, 44)),
+                                               (64, 48, (48, 1333), (48, 64)), (514, 64, (32, 1333), (32, 257))])
+def test_device_transform_flat_frames_and_batches(model, w, h, resize, out_hw):
+    """all-0, all-255 and checkerboard frames (the accumulators' extremes and the rounding constant of each pass), bit for bit; the
+    same frame alone and four times in a batch gives identical planes"""
+    from odam_amd import transforms
+    det, _ = model
+    assert transforms.target_size(w, h, *resize) == out_hw
+    rng = np.random.default_rng(w + h)
+    board = (np.add.outer(np.arange(h), np.arange(w)) % 2 * 255).astype(np.uint8)
+    imgs = np.stack([np.zeros((h, w, 3), np.uint8), np.full((h, w, 3), 255, np.uint8), np.repeat(board[..., None], 3, 2),
+                     rng.integers(0, 256, (h, w, 3), dtype=np.uint8)])
+    imgs[2, ..., 1] = 255 - imgs[2, ..., 1]          # the green plane in opposite phase
+    host = torch.stack([transforms.Transforms(*resize)(im)[0] for im in imgs])
+    det.resize = resize
+    try:
+        got = det.preprocess_u8(torch.from_numpy(imgs).to(DEV)).cpu()
+        one = det.preprocess_u8(torch.from_numpy(imgs[3:4]).to(DEV)).cpu()
+        four = det.preprocess_u8(torch.from_numpy(np.repeat(imgs[3:4], 4, 0)).to(DEV)).cpu()
+    finally:
+        det.resize = (800, 1333)
+    assert torch.equal(got, host), _transform_diff(got, host)
+    assert one.shape == (1, 3) + out_hw and four.shape == (4, 3) + out_hw
+    for b in range(4):
+        assert torch.equal(four[b], one[0])
+    assert torch.equal(one[0], host[3])
 
 
 def test_streamed_detection_from_raw_frames(model):
