@@ -117,8 +117,51 @@ int odam_assoc_step(odam_assoc* m, odam_trackwin* w, struct odam_sq_ctx* sq, int
 int odam_assoc_stage_stamps(odam_assoc* m, int enable, unsigned long long* out, int n);
 
 /* diagnostics: copies a workspace buffer of the last forward to out [host][n]: which = 0 the row block X [(T+30), 512],
- * 1 the descriptors [(T+30), 256], 2 the score matrix [T, 32] (synchronises the device) */
+ * 1 the descriptors [(T+30), 256], 2 the score matrix [T, 32]; of the last odam_assoc_forward_batch: 3 the padded row block as
+ * assembled [(B Tmax + 30 B), 256] (the B Tmax track rows, then the 30 B detection rows), 4 its descriptors, same shape, 5 its
+ * score blocks [sum T, 32] (sample after sample; columns 30 and 31 are not written) (synchronises the device) */
 int odam_assoc_debug_read(odam_assoc* m, int which, float* out, long long n);
+
+/* ---- the batched forward with the validation loss (src/models/associator.py:202-268 with eval_only = False) ----
+ *
+ * odam_assoc_ot_batch -- log_optimal_transport and the loss gather of B score blocks in ONE launch, one workgroup per sample.
+ *   Device arrays [B]: score_off (element offset of the sample's [m_b, n_b] block in scores), lds (its row stride >= n_b), m, n,
+ *   Z_off (element offset of its dense (m_b+1) x (n_b+1) block in Z_out).  alpha = bin_score for the dustbin row and column.
+ *   gt [dev] int32 [sum k][2] = (track, detection) pairs, gt_off [dev] int32 [B+1]; an index of -1 means the dustbin, like the
+ *   reference's negative index, and so do m_b and n_b.  k_b = 0 is allowed; gt = gt_off = null means no pairs at all.
+ *   loss_terms [dev] float64 [B] = sum over the sample's pairs, in pair order and in binary64, of -Z_b[track, detection].
+ *   status [dev] int32 [B]: bit 0 (1) Z_b holds a NaN -- its loss term is 0 (associator.py:254-255); bit 1 (2) the sample is outside
+ *   1 <= m_b <= max_m, 1 <= n_b <= 30, lds_b >= n_b: nothing of it is written but status and a zero loss term; bit 2 (4) a pair
+ *   outside [-1, m_b] x [-1, n_b] was left out of the sum.
+ *   max_m [host] bounds every m_b (it sizes the workgroup and its LDS).  A sample's Z and loss term are the same bits wherever it
+ *   stands in the batch, whatever else the batch holds and whatever max_m is.
+ *   Refused before the device is touched: null pointers, gt without gt_off, iters < 0 (code 1); B outside 1 .. 64, max_m outside
+ *   1 .. 1024 (code 3).  Stream-ordered, no host synchronisation.
+ *
+ * odam_assoc_reserve_batch -- workspaces of the padded row block for max_batch samples of up to max_tracks_per_sample tracks:
+ *   max_batch (max_tracks_per_sample + 30) rows.  Keeps a reservation that is already large enough; otherwise synchronises the device.
+ *   1 <= max_batch <= 64, 1 <= max_tracks_per_sample <= 1024 (code 3).
+ *
+ * odam_assoc_forward_batch -- tracks [dev][sum T, 79, 100], the tracks of sample 0, then of sample 1, ...; detections [dev][B, 79, 30]
+ *   (slots past n_det_b hold the collater's -1); T, n_det [host][B]; gt [host] int32 [sum k][2], gt_off [host][B+1] (both null: no loss);
+ *   Z_off [host][B]: element offset of sample b's dense (T_b+1) x (n_det_b+1) block in Z_out [dev]; loss_terms [dev] float64 [B],
+ *   status [dev] int32 [B] as above.  Encoder and fuser over all 100 sum T + 30 B rows, the time means into the block
+ *   [B Tmax track rows | 30 B detection rows] with every column of a padding row at -1 (_reshape_tracks), the matching layers as the
+ *   launch sequence over that block with two batched attention launches per layer, the final projection, the score blocks and
+ *   odam_assoc_ot_batch.  The padding rows are keys and queries of every matching layer, as in the reference: a sample's result
+ *   depends on the largest track count of its batch.
+ *   Refused before the device is touched: null pointers, gt without gt_off, gt_off not starting at 0 or decreasing, a pair outside
+ *   [-1, T_b] x [-1, n_det_b] (code 1); B outside 1 .. 64, a T_b < 1, an n_det_b outside 1 .. 30, sum T > 1024, sum T > the handle's
+ *   max_tracks, more than 4096 pairs, a padded block of B (Tmax + 30) rows larger than the reservation (code 3).
+ *   Stream-ordered, no allocation; the host arrays are copied before the call returns (a pinned ring of four slots whose reuse waits
+ *   for the upload issued from that slot, as odam_trackwin_append's).  One handle serves one stream at a time. */
+int odam_assoc_ot_batch(const float* scores, const long long* score_off, const int* lds, const int* m, const int* n, int B, int max_m,
+                        float alpha, int iters, const int* gt, const int* gt_off, float* Z_out, const long long* Z_off, double* loss_terms,
+                        int* status, void* stream);
+int odam_assoc_reserve_batch(odam_assoc* m, int max_batch, int max_tracks_per_sample);
+int odam_assoc_forward_batch(odam_assoc* m, const float* tracks, const int* T, const float* detections, const int* n_det, int B,
+                             const int* gt, const int* gt_off, float* Z_out, const long long* Z_off, double* loss_terms, int* status,
+                             void* stream);
 
 /* hungarian_matching (src/models/associator.py:19-35) on the device, stream-ordered: the assignment scipy.optimize.linear_sum_assignment
  * returns for the cost matrix 1 - scores (its shortest-augmenting-path solver restated with its tie order, binary64 duals), scores = exp(Z)

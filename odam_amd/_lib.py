@@ -61,6 +61,16 @@ def set_config(key, value):
     check(lib().odam_config_set(key.encode(), ctypes.c_int(int(value))), f"odam_config_set({key})")
 
 
+# Argument types of the entries whose pointer arguments are handed over as plain addresses (a Python int would otherwise be
+# truncated to a C int): the batched association forward (include/odam_assoc.h).
+_I, _P, _F = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
+_PROTOTYPES = {
+    "odam_assoc_ot_batch": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
+    "odam_assoc_reserve_batch": [_P, _I, _I],
+    "odam_assoc_forward_batch": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+}
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -74,6 +84,9 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         L.odam_last_error.restype = ctypes.c_char_p
+        for name, argtypes in _PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, ctypes.c_int
         _apply_env(L)
         _lib = L
     return _lib

@@ -392,10 +392,14 @@ class Associator:
         return self._pin[1][:(n_tracks + 1) * (n_det + 1)].view(n_tracks + 1, n_det + 1)
 
     def __call__(self, in_data, threshold, eval_only=False, device="cuda"):
-        """Associator.forward for the batch-of-one call of OdamProcess (associator.py:202-268, eval_only=True)"""
+        """Associator.forward (associator.py:202-268) for any batch: in_data["tracks"] [sum T, 79, 100], ["detections"] [B, 79, 30],
+        ["valid_list"] [(T_b, n_det_b)] * B and, unless eval_only, ["gt_matches"] [[k_b, 2] (track, detection) index pairs] * B, where -1
+        (like T_b / n_det_b) names the dustbin.  Returns "pred" [Z_b[None]] * B, "loss" (0-dim float64 tensor: sum over the samples of
+        sum_pairs -Z_b[track, detection]), "matches" [per detection: track id, -1 = new] * B and "loss_terms" (float64 [B]).
+        The batch-of-one inference call of OdamProcess (eval_only=True) keeps its own path: the persistent matching kernel."""
         valid = in_data["valid_list"]
-        if len(valid) != 1:
-            raise _lib.OdamError("batch size 1 only (what OdamProcess.process_frame passes)")
+        if len(valid) != 1 or not eval_only:
+            return self._call_batch(in_data, threshold, eval_only)
         n_tracks, n_det = valid[0]
         # ONE download of the log assignment: both consumers -- the Hungarian step here and process_frame's score matrix
         # (processor.py:337-339: predictions['pred'][0][0].cpu().exp()) -- read it on the host
@@ -409,7 +413,152 @@ class Associator:
             match = [hungarian_matching(Z[:-1, :-1].exp(), threshold)]
         return {"pred": pred, "loss": 0, "matches": match}
 
+    MAX_BATCH = 64         # odam_assoc_forward_batch's limits (include/odam_assoc.h)
+    MAX_DETS = 30
+
+    def forward_batch(self, tracks, detections, valid_list, gt_matches=None):
+        """The batched forward on the device, stream-ordered (odam_assoc_forward_batch): -> (Z flat float32 device tensor, Z_off
+        [B + 1] element offsets of the dense (T_b + 1) x (n_b + 1) blocks, loss_terms float64 [B] device, status int32 [B] device).
+        gt_matches None: no pairs (the loss terms are 0)."""
+        dev = self.device
+        valid = [(int(t), int(n)) for t, n in valid_list]
+        B = len(valid)
+        sum_t, t_max = sum(t for t, _ in valid), max([t for t, _ in valid] + [1])
+        tr = tracks.to(dev, torch.float32).contiguous()
+        de = detections.to(dev, torch.float32).contiguous()
+        if tuple(tr.shape) != (sum_t, 79, TrackWindows.WINDOW) or tuple(de.shape) != (B, 79, self.MAX_DETS):
+            raise _lib.OdamError(f"Associator: tracks {tuple(tr.shape)} / detections {tuple(de.shape)} do not fit valid_list "
+                                 f"({sum_t} tracks, {B} samples): expected [{sum_t}, 79, 100] and [{B}, 79, 30]")
+        T = np.ascontiguousarray([t for t, _ in valid], np.int32)
+        n = np.ascontiguousarray([k for _, k in valid], np.int32)
+        gt = gt_off = None
+        if gt_matches is not None:
+            if len(gt_matches) != B:
+                raise _lib.OdamError(f"Associator: {len(gt_matches)} gt_matches for {B} samples")
+            pairs = [np.asarray(g.cpu() if torch.is_tensor(g) else g).astype(np.int32).reshape(-1, 2) for g in gt_matches]
+            gt = np.ascontiguousarray(np.concatenate(pairs, axis=0) if pairs else np.zeros((0, 2)), np.int32)
+            if gt.shape[0] == 0:
+                gt = np.zeros((1, 2), np.int32)      # (a non-null address; gt_off says it holds nothing)
+            gt_off = np.ascontiguousarray(np.r_[0, np.cumsum([len(p) for p in pairs])], np.int32)
+        z_off = np.ascontiguousarray(np.r_[0, np.cumsum([(t + 1) * (k + 1) for t, k in valid])], np.int64)
+        if 1 <= sum_t <= self.MAX_TRACKS and sum_t > self.max_tracks:
+            self._grow(sum_t)
+        h = self._handle()
+        L = _lib.lib()
+        addr = lambda a: None if a is None else a.ctypes.data
+        with torch.cuda.device(dev):
+            if 1 <= B <= self.MAX_BATCH and t_max <= self.MAX_TRACKS and B * (t_max + self.MAX_DETS) > (self._batch_rows if getattr(self, "_batch_h", None) is h else 0):
+                # the padded block's workspaces, sized the way _grow sizes the handle: at least twice the room that ran out
+                b_cap, t_cap = getattr(self, "_batch_cap", (0, 0))
+                b_cap, t_cap = min(self.MAX_BATCH, max(B, b_cap)), min(self.MAX_TRACKS, max(t_max, t_cap))
+                _lib.check(L.odam_assoc_reserve_batch(h, b_cap, t_cap), "odam_assoc_reserve_batch")
+                self._batch_cap, self._batch_rows, self._batch_h = (b_cap, t_cap), b_cap * (t_cap + self.MAX_DETS), h
+            Z = torch.empty(max(int(z_off[-1]), 1), device=dev, dtype=torch.float32)
+            terms = torch.zeros(max(B, 1), device=dev, dtype=torch.float64)
+            status = torch.zeros(max(B, 1), device=dev, dtype=torch.int32)
+            _lib.check(L.odam_assoc_forward_batch(h, tr.data_ptr(), addr(T), de.data_ptr(), addr(n), B, addr(gt), addr(gt_off), Z.data_ptr(),
+                                                  addr(z_off), terms.data_ptr(), status.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream), "odam_assoc_forward_batch")
+        return Z, z_off, terms[:B], status[:B]
+
+    def _call_batch(self, in_data, threshold, eval_only):
+        if "valid_list" not in in_data or (not eval_only and "gt_matches" not in in_data):
+            raise KeyError("Associator: valid_list is required, and gt_matches unless eval_only")
+        valid = [(int(t), int(n)) for t, n in in_data["valid_list"]]
+        B = len(valid)
+        dev = self.device
+        Z, z_off, terms, status = self.forward_batch(in_data["tracks"], in_data["detections"], valid, None if eval_only else in_data["gt_matches"])
+        # matches: with assoc.hungarian = 1 the samples inside the device solver's 32 x 128 are solved behind the transport, one wavefront
+        # each; every other sample by scipy on the host, from the one download of all Z blocks below
+        on_device = []
+        if _lib.get_config("assoc.hungarian"):
+            on_device = [b for b, (t, n) in enumerate(valid) if min(t, n) <= 32 and max(t, n) <= 128]
+        if on_device:
+            pin = torch.empty(B * 33, dtype=torch.int32).pin_memory()      # 32 match words + the status word per sample
+            L = _lib.lib()
+            with torch.cuda.device(dev):
+                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                for b in on_device:
+                    t, n = valid[b]
+                    _lib.check(L.odam_assoc_hungarian(ctypes.c_void_p(Z.data_ptr() + 4 * int(z_off[b])), ctypes.c_int(t), ctypes.c_int(n),
+                                                      ctypes.c_int(n + 1), ctypes.c_double(float(threshold)), ctypes.c_int(1),
+                                                      ctypes.c_void_p(pin.data_ptr() + 4 * 33 * b), ctypes.c_void_p(pin.data_ptr() + 4 * (33 * b + 32)),
+                                                      stream), "odam_assoc_hungarian")
+        Zh, terms_h, status_h = Z.cpu(), terms.cpu(), status.cpu()      # (synchronises the stream)
+        torch.cuda.current_stream(dev).synchronize()
+        pred, matches = [], []
+        for b, (t, n) in enumerate(valid):
+            if int(status_h[b]) & 1:
+                raise ValueError(f"Associator: the log assignment of sample {b} ({t} tracks, {n} detections) holds a NaN")
+            if int(status_h[b]):
+                raise _lib.OdamError(f"Associator: sample {b} was refused by odam_assoc_ot_batch (status {int(status_h[b])})")
+            Zb = Zh[int(z_off[b]):int(z_off[b + 1])].view(t + 1, n + 1)
+            pred.append(Zb[None])
+            if b in on_device and int(pin[33 * b + 32]) == 0:
+                matches.append(pin[33 * b:33 * b + n].numpy().astype(np.float64))
+            else:
+                matches.append(hungarian_matching(Zb[:-1, :-1].exp(), threshold))
+        total = 0.0
+        for x in terms_h.tolist():      # in sample order: loss == sum(loss_terms)
+            total += x
+        return {"pred": pred, "loss": torch.tensor(total, dtype=torch.float64), "matches": matches, "loss_terms": terms_h}
+
     forward = __call__
+
+
+def collate(data_list):
+    """The reference's collater (src/scripts/run_association.py:68-123, src/datasets/scan_net_track.py): samples
+    {"tracks" [T, 79, 100], "detections" [79, n <= 30], "match" [k, 2], "img_path", "pose"} -> one batch with its key set.  The
+    detection slots past n are padded with -1 up to max_dets = 30; gt_masks [sum T, sum n] is 1 inside every sample's own block."""
+    max_dets = Associator.MAX_DETS
+    B = len(data_list)
+    n_features = data_list[0]["detections"].shape[0]
+    detections = torch.full((B, n_features, max_dets), -1.0, dtype=torch.float)
+    track_split = [int(d["tracks"].shape[0]) for d in data_list]
+    det_split = [int(d["detections"].shape[1]) for d in data_list]
+    for b, d in enumerate(data_list):
+        detections[b, :, :det_split[b]] = torch.as_tensor(d["detections"], dtype=torch.float)
+    gt_masks = torch.zeros((sum(track_split), sum(det_split)), dtype=torch.float)
+    t0 = d0 = 0
+    for nt, nd in zip(track_split, det_split):
+        gt_masks[t0:t0 + nt, d0:d0 + nd] = 1
+        t0, d0 = t0 + nt, d0 + nd
+    return {"tracks": torch.cat([torch.as_tensor(d["tracks"]) for d in data_list], dim=0),
+            "detections": detections,
+            "gt_matches": [d["match"] for d in data_list],
+            "gt_masks": gt_masks,
+            "img_names": [d.get("img_path") for d in data_list],
+            "track_batch_split": track_split,
+            "detection_batch_split": det_split,
+            "poses": [d.get("pose") for d in data_list],
+            "valid_list": list(zip(track_split, det_split))}
+
+
+def gt_track_of_detections(match, n_tracks, n_det):
+    """[n_det] ground-truth track of every detection from the (track, detection) pairs of a sample: -1 (new) where the pair names the
+    track dustbin (-1 or n_tracks) or no pair names the detection; pairs on the detection dustbin say nothing about a detection"""
+    out = np.full(n_det, -1.0)
+    for t, d in np.asarray(match).reshape(-1, 2).astype(np.int64):
+        if 0 <= d < n_det:
+            out[d] = t if 0 <= t < n_tracks else -1
+    return out
+
+
+def validate(model, samples, threshold, batch_size):
+    """Scores `model` (an Associator with its weights loaded) on recorded samples (collate()'s input) in batches of batch_size:
+    "loss" = the mean over the samples of sum_pairs -Z[track, detection] -- the unit of the reference's training log per sample --, "accuracy"
+    = the share of detections whose predicted track equals the ground-truth track (-1 = new); per sample: "loss_terms", "correct", "n_det"."""
+    terms, correct, n_dets = [], [], []
+    for i0 in range(0, len(samples), batch_size):
+        chunk = samples[i0:i0 + batch_size]
+        batch = collate(chunk)
+        out = model(batch, threshold, eval_only=False)
+        terms += out["loss_terms"].tolist()
+        for (t, n), match, pred in zip(batch["valid_list"], batch["gt_matches"], out["matches"]):
+            correct.append(int((np.asarray(pred) == gt_track_of_detections(match, t, n)).sum()))
+            n_dets.append(n)
+    return {"loss": float(np.sum(terms) / max(len(terms), 1)), "accuracy": float(sum(correct) / max(sum(n_dets), 1)),
+            "loss_terms": terms, "correct": correct, "n_det": n_dets}
 
 
 def build(args):

@@ -34,11 +34,6 @@ namespace {
 
 constexpr int D = 256, NF = 79, NT = 100, ND = 30, FPAD = 128;
 
-struct Lin { float* w = nullptr; float* b = nullptr; int K = 0, N = 0; };
-struct Prop { Lin qkv, merge, m0, m2; };   // AttentionalPropagation (associator.py:85-97); q, k, v stacked
-
-struct HostT { std::vector<long long> shape; std::vector<float> data; };
-
 // ---- kernels ------------------------------------------------------------------------------------------------------
 // in [n_seq, 79, L] channel-first (row 0 = frame index, rows 1..78 features) ->
 // feat [n_seq*L, 128] (features, zero padded) and cat[:, 0:256] = sine encoding of the frame index
@@ -418,54 +413,10 @@ int lin(const Lin& L, const float* x, int lda, int M, const float* res, bool rel
 
 }  // namespace
 
-struct odam_assoc {
-    int max_tracks = 0, n_self = 0, n_gnn = 0, iters = 100;
-    std::vector<int> gnn_cross;          // per GNN layer: 1 = cross
-    std::map<std::string, HostT> host;
-    bool finalized = false;
-    std::vector<void*> allocs;
-    Lin enc0, enc2, final_proj;
-    std::vector<Prop> fuser, gnn;
-    float bin_score = 1.0f;
-    float *div_term = nullptr, *sc16 = nullptr;
-    // workspace
-    float *feat = nullptr, *h256 = nullptr, *catT = nullptr, *kv = nullptr, *att = nullptr, *h512 = nullptr;
-    float *kvX = nullptr, *kvX2 = nullptr, *attX = nullptr, *hX = nullptr;
-    float *catTr = nullptr, *mT = nullptr, *scores = nullptr;
-    // persistent matching kernel: barrier counters (+ error flag), zeroed on the stream before every launch
-    unsigned* bar = nullptr;
-    bool persist = true;
-    int resident_capacity = 0;               // workgroups of the persistent kernel the device can hold at once (with the guide's margin)
-    unsigned long long timeout_ticks = 2000000ull;   // 20 ms per barrier wait (100 MHz ticks); a healthy wait is ~2 us, ~1 ms under a saturated device
-    unsigned* lost_count = nullptr;          // pinned host word: launches abandoned at a barrier so far (the Sinkhorn kernel bumps it)
-    unsigned long long* stamps = nullptr;    // device, 128 entries; written only while want_stamps
-    bool want_stamps = false;
-    bool fake_misplaced = false;             // tests: odam_assoc_debug_misplace
-    bool bar_clean = false;                  // the counters are zero: the one-wavefront Sinkhorn kernel zeroes them behind the launch that used them
-    bool merged = false;                     // odam_config assoc.merge as read by odam_assoc_finalize: every Prop's m0 holds the merge projection too
-
-    // Zeroing goes through a private non-blocking stream that finalize waits for: hipMemset would be ordered on the NULL stream -- it
-    // may still be pending when it returns (and then land behind the first results of a caller that works on a stream of its own),
-    // and waiting for the NULL stream instead would wait for whatever another thread has queued there (a detector's chunk copies).
-    hipStream_t init_stream = nullptr;
-    int alloc(float** p, size_t n) {
-        ODAM_HIP(hipMalloc((void**)p, n * sizeof(float)));
-        if (!init_stream) ODAM_HIP(hipStreamCreateWithFlags(&init_stream, hipStreamNonBlocking));
-        ODAM_HIP(hipMemsetAsync(*p, 0, n * sizeof(float), init_stream));
-        allocs.push_back(*p);
-        return 0;
-    }
-    int init_done() {
-        if (init_stream) { ODAM_HIP(hipStreamSynchronize(init_stream)); ODAM_HIP(hipStreamDestroy(init_stream)); init_stream = nullptr; }
-        return 0;
-    }
-    int upload(float** p, const std::vector<float>& v) {
-        if (int rc = alloc(p, v.size())) return rc;
-        ODAM_HIP(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, init_stream));   // behind the memset of the same buffer
-        ODAM_HIP(hipStreamSynchronize(init_stream));        // v may be a temporary
-        return 0;
-    }
-};
+int odam_assoc_internal::assoc_lin(const Lin& L, const float* x, int lda, int M, const float* res, bool relu, float* y, int ldc,
+                                   const float* scale, hipStream_t st) {
+    return lin(L, x, lda, M, res, relu, y, ldc, scale, st);
+}
 
 namespace {
 
@@ -582,6 +533,7 @@ extern "C" int odam_assoc_create(int max_tracks, int n_self_layers, const int* g
 extern "C" int odam_assoc_destroy(odam_assoc* m) {
     if (!m) return 0;
     if (m->lost_count) (void)hipHostFree(m->lost_count);
+    batch_release(m);
     if (m->init_stream) { (void)hipStreamSynchronize(m->init_stream); (void)hipStreamDestroy(m->init_stream); }
     for (void* p : m->allocs) (void)hipFree(p);
     delete m;
@@ -627,7 +579,9 @@ extern "C" int odam_assoc_finalize(odam_assoc* m) {
         m->gnn.push_back(P);
     }
     const size_t T = m->max_tracks, N = T * NT;
-    RC(m->alloc(&m->feat, (N + ND) * FPAD)); RC(m->alloc(&m->h256, (N + ND) * D)); RC(m->alloc(&m->catT, (N + ND) * 512));      // + the 30 detection rows behind the tracks'
+    // + the 30 detection rows behind the tracks', of every sample of a batched forward (assoc_batch.hip)
+    constexpr size_t NDB = (size_t)ND * MAX_BATCH;
+    RC(m->alloc(&m->feat, (N + NDB) * FPAD)); RC(m->alloc(&m->h256, (N + NDB) * D)); RC(m->alloc(&m->catT, (N + NDB) * 512));
     RC(m->alloc(&m->kv, N * 768)); RC(m->alloc(&m->att, N * D)); RC(m->alloc(&m->h512, N * 512));
     // fused tracks [T] and the 30 detection slots share one row block (detections start at row T of the frame) so the
     // shared-weight GNN layers see both sets as ONE matrix
@@ -669,24 +623,29 @@ extern "C" int odam_assoc_finalize(odam_assoc* m) {
     return 0;
 }
 
-// the launch sequence of one forward: ~65 kernels, every one a memory round trip long at these sizes (<= 70 rows)
-static int enqueue_forward(odam_assoc* m, const float* tracks, int T, const float* detections, int n_det, float* Z_out, hipStream_t st,
-                           bool allow_persist = true) {
-    const int N = T * NT;
-    // encoder + frame-index encoding (associator.py:222-229)
-    float* X = m->catTr;                      // [T + 30][512]: fused tracks, then the detection slots (rows T ..)
-    const int MX = T + ND;
+// encoder + frame-index encoding (associator.py:222-229) and the fuser, for one frame (n_det_rows = 30) or a batch of them
+int odam_assoc_internal::encode_and_fuse(odam_assoc* m, const float* tracks, int T, const float* detections, int n_det_rows, hipStream_t st) {
+    const int N = T * NT, NDR = n_det_rows;
     // The detections go through the encoder as 30 more rows of the tracks' matrix (rows N .. N + 29 of feat / catT: same weights, rows are
     // independent, and the same tile shape serves 30 and 100 T + 30 rows -- one launch per layer instead of two); time_mean_kernel moves
     // their encodings behind the track means afterwards.
     // (the same three launches on a second stream beside the tracks' branch, forked and joined by events: measured, no change; not kept)
-    hipLaunchKernelGGL(prepare_kernel, dim3(N + ND), dim3(256), 0, st, tracks, NT, N, m->div_term, m->feat, m->catT, detections, ND, ND);
+    hipLaunchKernelGGL(prepare_kernel, dim3(N + NDR), dim3(256), 0, st, tracks, NT, N, m->div_term, m->feat, m->catT, detections, ND, NDR);
     ODAM_HIP(hipGetLastError());
-    RC(lin(m->enc0, m->feat, FPAD, N + ND, nullptr, true, m->h256, D, nullptr, st));
-    RC(lin(m->enc2, m->h256, D, N + ND, m->catT, false, m->catT, 512, nullptr, st));           // + pe, in place
+    RC(lin(m->enc0, m->feat, FPAD, N + NDR, nullptr, true, m->h256, D, nullptr, st));
+    RC(lin(m->enc2, m->h256, D, N + NDR, m->catT, false, m->catT, 512, nullptr, st));           // + pe, in place
     // fuser: self-attention over each track's 100 time steps (associator.py:143-160, 230)
     for (const Prop& P : m->fuser)
         RC(prop_forward_self(P, m->catT, N, T, NT, m->kv, m->att, m->h512, st, m->merged));
+    return 0;
+}
+
+// the launch sequence of one forward: ~65 kernels, every one a memory round trip long at these sizes (<= 70 rows)
+static int enqueue_forward(odam_assoc* m, const float* tracks, int T, const float* detections, int n_det, float* Z_out, hipStream_t st,
+                           bool allow_persist = true) {
+    float* X = m->catTr;                      // [T + 30][512]: fused tracks, then the detection slots (rows T ..)
+    const int MX = T + ND;
+    RC(encode_and_fuse(m, tracks, T, detections, ND, st));
     hipLaunchKernelGGL(time_mean_kernel, dim3(T + ND), dim3(256), 0, st, m->catT, NT, X, T);
     ODAM_HIP(hipGetLastError());
     // matching GNN between the fused tracks [T] and all 30 detection slots (associator.py:111-139, 240).  Both sets
@@ -830,8 +789,10 @@ extern "C" int odam_assoc_stage_stamps(odam_assoc* m, int enable, unsigned long 
 }
 
 // diagnostics: a workspace buffer of the last forward ([host] out[n]): 0 = row block X [(T + 30), 512], 1 = descriptors mT
-// [(T + 30), 256], 2 = scores [T, 32]
+// [(T + 30), 256], 2 = scores [T, 32]; of the last BATCHED forward (assoc_batch.hip): 3 = the padded row block as assembled
+// [(B Tmax + 30 B), 256], 4 = its descriptors [(B Tmax + 30 B), 256], 5 = its score blocks [sum T, 32]
 extern "C" int odam_assoc_debug_read(odam_assoc* m, int which, float* out, long long n) {
+    if (m && m->finalized && out && n > 0 && which >= 3 && which <= 5) return batch_debug_read(m, which, out, n);
     if (!m || !m->finalized || !out || n <= 0 || which < 0 || which > 2) return odam_fail(1, "odam_assoc_debug_read: bad argument");
     const float* src = which == 0 ? m->catTr : (which == 1 ? m->mT : m->scores);
     ODAM_HIP(hipDeviceSynchronize());
