@@ -62,9 +62,15 @@ def set_config(key, value):
 
 
 # Argument types of the entries whose pointer arguments are handed over as plain addresses (a Python int would otherwise be
-# truncated to a C int): the batched association forward (include/odam_assoc.h).
+# truncated to a C int): the batched association forward (include/odam_assoc.h) and the scene table of its validation samples.
 _I, _P, _F = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
+_L, _D = ctypes.c_longlong, ctypes.c_double
 _PROTOTYPES = {
+    # the scene table of the validation samples (include/odam_samples.h)
+    "odam_samples_create": [_I, _I, _L, _L, _P],
+    "odam_samples_destroy": [_P],
+    "odam_samples_load": [_P, _P, _P, _P, _P, _P, _P, _D, _D, _P],
+    "odam_samples_cut": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "odam_assoc_ot_batch": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     "odam_assoc_reserve_batch": [_P, _I, _I],
     "odam_assoc_forward_batch": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],

@@ -561,6 +561,23 @@ def validate(model, samples, threshold, batch_size):
             "loss_terms": terms, "correct": correct, "n_det": n_dets}
 
 
+def validate_scene(model, scene, threshold, batch_size=16, frames=None, use_gt_det=False):
+    """validate() on a labelled scene (assoc_samples.SceneTable): every batch of frames is cut on the device (SceneTable.cut: one launch,
+    straight into the batched forward's layout) and scored by model(batch, threshold, eval_only=False); the tracks tensor never visits the
+    host.  frames None: every usable frame of the scene.  Returns validate()'s dict plus "frames"."""
+    frames = scene.usable_frames(use_gt_det) if frames is None else [int(f) for f in frames]
+    terms, correct, n_dets = [], [], []
+    for chunk in scene.batches(frames, batch_size):
+        batch = scene.cut(chunk, use_gt_det=use_gt_det)
+        out = model(batch, threshold, eval_only=False)
+        terms += out["loss_terms"].tolist()
+        for (t, n), match, pred in zip(batch["valid_list"], batch["gt_matches"], out["matches"]):
+            correct.append(int((np.asarray(pred) == gt_track_of_detections(match, t, n)).sum()))
+            n_dets.append(n)
+    return {"loss": float(np.sum(terms) / max(len(terms), 1)), "accuracy": float(sum(correct) / max(sum(n_dets), 1)),
+            "loss_terms": terms, "correct": correct, "n_det": n_dets, "frames": frames}
+
+
 def build(args):
     """src/models/associator.py:330-340"""
     g = (lambda k: args[k]) if isinstance(args, dict) else (lambda k: getattr(args, k))
