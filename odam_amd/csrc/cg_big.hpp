@@ -1188,12 +1188,10 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
     else epilogue<BM, BN, WM, WN, TM, TN, BF16>(a, acc, smem, big_lds_bytes<MODE, BN, NST, NTH>() / 4, m0, n0, wm, wn, wave, lane);
 }
 
-#define g_s1_window odam_cfg::get(odam_cfg::CG_S1)      // bf16 3x3 stride 1: window main loop (0: the generic tap gather)
-
 template <int MODE, int BN, int NST, int NTH = 512>
-static int launch_big(const ConvGemmArgs& a_in, hipStream_t stream) {
+static int launch_big(const ConvGemmArgs& a_in, int s1_window, hipStream_t stream) {
     ConvGemmArgs a = a_in;
-    a.s1_window = (MODE == 0 && NTH == 512) ? g_s1_window : 0;
+    a.s1_window = s1_window;
     constexpr int bytes = big_lds_bytes<MODE, BN, NST, NTH>();
     static const bool attr_ok = [] {
         return hipFuncSetAttribute((const void*)conv_gemm_big_kernel<MODE, BN, NST, NTH>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;

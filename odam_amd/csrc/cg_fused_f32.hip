@@ -22,10 +22,7 @@ static int launch_big_fused_as(const ConvGemmArgs& a, hipStream_t stream) {
     ODAM_HIP(hipGetLastError());
     return 0;
 }
-int launch_big_fused(const ConvGemmArgs& a, hipStream_t stream) {
-    const int m16 = odam_cfg::get(odam_cfg::CG_MFMA16);      // 2: the 128-column bottleneck launches too, 3: the 64-column ones as well
-    const bool x16 = a.Kpad % 32 == 0 && (m16 >= 3 || (m16 == 2 && a.Cout == 128));
-    note_path("f32.fused.m%d.%s", x16 ? 4 : 3, a.Cout == 128 ? "l2" : !a.G_Wt3 ? "l1" : a.G_N == 128 ? "chain128" : "chain64");
+int launch_big_fused(int mode, const ConvGemmArgs& a, hipStream_t stream) {
     // The tails address the residual and the output through buffer descriptors with 31-bit byte offsets from F_res / F_C.  A batch
     // whose output reaches 2 GiB (layer1 from 40 frames of 800 x 1066) runs as one launch per group of whole images, with the
     // pointers offset to the group's first image: a row's products, order and roundings do not depend on the tile it falls in,
@@ -42,7 +39,7 @@ int launch_big_fused(const ConvGemmArgs& a, hipStream_t stream) {
         if (a.F_res) g.F_res = a.F_res + (size_t)b0 * img_rows * a.F_ldc;
         g.F_C = a.F_C + (size_t)b0 * img_rows * a.F_ldc;
         if (a.G_C) g.G_C = a.G_C + (size_t)b0 * img_rows * a.G_N;
-        const int rc = x16 ? launch_big_fused_as<4>(g, stream) : launch_big_fused_as<3>(g, stream);
+        const int rc = mode == 4 ? launch_big_fused_as<4>(g, stream) : launch_big_fused_as<3>(g, stream);
         if (rc) return rc;
     }
     return 0;

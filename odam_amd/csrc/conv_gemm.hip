@@ -375,9 +375,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(ConvGemmArgs a)
     else epilogue<BM, BN, WM, WN, TM, TN, BF16>(a, acc, smem, (int)sizeof(smem) / 4, m0, n0, wm, wn, wave, lane);
 }
 
-#define g_big_mode odam_cfg::get(odam_cfg::CG_RING)      // 0 off, 1 auto, 2 whenever eligible
-void set_big_mode(int mode) { odam_cfg::set(odam_cfg::CG_RING, mode); }
-
 void split3_filters(const float* w, int Cout, int Kpad, unsigned short* out) {
     const int nk = Kpad / 16;
     for (int n = 0; n < Cout; n++)
@@ -398,173 +395,39 @@ void split3_filters(const float* w, int Cout, int Kpad, unsigned short* out) {
         }
 }
 
-// the bf16-native kernel takes a layer when its gather is uniform-tap at k-tile 32 and the problem is large enough
-// to give every CU a 256-row tile with a K loop worth pipelining
-// fp32 layers on the 256-row kernel: 0 = no (128x128 tiles on the fp32 matrix instruction), 2 = products on the bf16 matrix
-// instruction through the exact three-way split (the default: same accuracy class as the fp32 instruction, every parity test
-// unchanged, 1.26x the R50 forward).  (1, the fp32 instruction inside the ring schedule, was measured slower than the 128x128
-// tiles and is gone.)
-#define g_big_f32 odam_cfg::get(odam_cfg::CG_F32)
-void set_f32_mode(int mode) { odam_cfg::set(odam_cfg::CG_F32, mode == 1 ? 0 : mode); }
-int f32_mode() { return g_big_mode ? g_big_f32 : 0; }
-// cg.pin: the choice a device-filling problem gets, whatever M is -- for callers whose row count depends on how a scene is sharded
-// (the detector); a caller whose rows are the same on every rank (the replicated association network) opts out with no_pin
-static inline bool pinned(const ConvGemmArgs& a) { return odam_cfg::get(odam_cfg::CG_PIN) != 0 && !a.no_pin; }
-static bool big_eligible(const ConvGemmArgs& a, int bn) {
-    const bool bf = a.dtype == ODAM_CG_BF16;
-    if (!bf && !g_big_f32) return false;
-    const int bke = bf ? 32 : 16, esz = bf ? 2 : 4;
-    if (a.Cin % bke != 0 || a.KH * a.KW > 32 || a.Kpad % bke != 0) return false;
-    if (a.k_order && a.Cin % (2 * bke) != 0) return false;
-    const long lda = a.lda > 0 ? a.lda : a.Cin;
-    const long span = (256L / ((long)a.Ho * a.Wo) + 2) * a.H * a.W * lda + (long)(a.pad * a.W + a.pad) * lda + a.Cin;
-    if (span * esz >= 0x7fffffffL || (long)a.Cout * a.Kpad * esz >= 0x7fffffffL) return false;
-    if (g_big_mode >= 2) return true;
-    if (pinned(a)) return a.Cout >= bn;      // the choice a device-filling problem gets, whatever M is
-    const long tiles = (long)((a.M + 255) / 256) * ((a.Cout + bn - 1) / bn);
-    return tiles >= 192 && a.Cout >= bn;     // short-K expand layers too: with 16-byte stores its one block per CU streams faster than two 128x128 blocks
-}
-
+// the small tiles: gather and products (Choice::ut, x3) as chosen; NST_UT = LDS stages of the LDS-DMA gather
 template <int BM, int BN, int WM, int WN, int NST_UT = 2>
-static int launch_cfg(const ConvGemmArgs& a, hipStream_t stream) {
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-    const bool bf = a.dtype == ODAM_CG_BF16;
-    // uniform-tap gather: whole k-tiles inside one tap, a 32-bit tap mask, and 31-bit byte offsets from the
-    // first image a tile touches (a tile spans at most BM / (Ho*Wo) + 2 images)
-    const long esz = bf ? 2 : 4, lda = a.lda > 0 ? a.lda : a.Cin;
-    const long span = ((long)BM / ((long)a.Ho * a.Wo) + 2) * a.H * a.W * lda + (long)(a.pad * a.W + a.pad) * lda + a.Cin;
-    const bool ut = odam_cfg::get(odam_cfg::CG_UT) != 0 && a.Cin % (bf ? 64 : 32) == 0 && a.KH * a.KW <= 32 && span * esz < 0x7fffffffL &&
-                    (long)a.Cout * a.Kpad * esz < 0x7fffffffL;
-    const dim3 g(tiles), b(64 * WM * WN);
-    const bool x3 = !bf && ut && g_big_f32 == 2 && odam_cfg::get(odam_cfg::CG_SMALL_X3) != 0;
-    note_path("%s.small.%dx%d.w%d%s%s%s", bf ? "bf16" : "f32", BM, BN, WM * WN, ut ? ".ut" : "", x3 ? ".x3" : "", ut && NST_UT == 4 ? ".s4" : "");
-    if (bf) {
-        if (ut) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, true, true, NST_UT>), g, b, 0, stream, a);
+static int launch_cfg(const ConvGemmArgs& a, const Choice& c, hipStream_t stream) {
+    const dim3 g(((a.M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN)), b(64 * WM * WN);
+    if (c.bf16) {
+        if (c.ut) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, true, true, NST_UT>), g, b, 0, stream, a);
         else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, true, false>), g, b, 0, stream, a);
     } else {
-        // fp32 split mode reaches the layers too small for the ring kernel as well (cg.small_x3): the same six exact products on
-        // v_mfma_f32_32x32x16_bf16, both operands split in registers.  Forward of 2 / 8 / 16 frames 4.89 -> 4.59 / 10.24 -> 9.66 /
-        // 17.36 -> 16.84 ms (same box, A/B by config); a batch of 32 has few such layers left (30.45 -> 30.32)
-        if (x3)
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, true, NST_UT, true>), g, b, 0, stream, a);
-        else if (ut) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, true, NST_UT>), g, b, 0, stream, a);
+        if (c.x3) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, true, NST_UT, true>), g, b, 0, stream, a);
+        else if (c.ut) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, true, NST_UT>), g, b, 0, stream, a);
         else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, false>), g, b, 0, stream, a);
     }
     ODAM_HIP(hipGetLastError());
     return 0;
 }
 
-// the fused kernel applies: fp32 split mode with pre-split filters on both layers, 64 -> 256 channels, a full device
-bool fused_second_ok(const ConvGemmArgs& a) {
-    const int fuse = odam_cfg::get(odam_cfg::CG_FUSE);
-    if (!fuse || !g_big_mode || g_big_f32 != 2 || a.dtype != ODAM_CG_F32) return false;
-    if (!a.F_Wt3 || !a.F_C || !a.Wt3 || a.Kpad % 16 != 0) return false;
-    const bool l1 = a.Cout == 64 && a.F_ldc == 256, l2 = a.Cout == 128 && a.F_ldc == 512 && !a.G_Wt3;     // the two shapes built
-    if ((!l1 && !l2) || a.dil != 1) return false;
-    // buffer descriptors over the output / residual: 31-bit byte offsets within ONE image (launch_big_fused runs a larger batch as
-    // groups of whole images, so that the choice does not depend on the batch)
-    if ((long)a.Cout * a.Kpad * 6 >= 0x7fffffffL || (long)a.Ho * a.Wo * a.F_ldc * 4 >= 0x7fffffffL) return false;
-    if (a.G_Wt3 && (fuse < 2 || !a.G_C || (a.G_N != 64 && a.G_N != 128))) return false;      // fuse 1: second layer only
-    return big_eligible(a, a.Cout);
-}
-
-// bf16: the 3x3 + expand (+ next reduce) kernel applies -- ring kernel eligible for the 3x3, the channel combination built,
-// residual / output tensors inside 31-bit byte offsets
-#define g_fuse_bf16 odam_cfg::get(odam_cfg::CG_FUSE_BF16)      // 0 off, 1 expand only, 2 with the chained reduce
-bool fused_bf16_ok(const ConvGemmArgs& a) {
-    if (!g_fuse_bf16 || !g_big_mode || a.dtype != ODAM_CG_BF16 || !a.F_Wt || !a.F_C) return false;
-    if (a.Cout != 64 && a.Cout != 128 && a.Cout != 256) return false;
-    if (a.F_ldc != 4 * a.Cout || a.KH * a.KW != 9 || a.Cin != a.Cout || !a.k_order || a.dil != 1) return false;
-    if ((long)a.M * a.F_ldc * 2 >= 0x7fffffffL) return false;
-    if (a.G_Wt) {
-        if (g_fuse_bf16 < 2 || !a.G_C) return false;
-        const bool built = (a.Cout == 64 && (a.G_N == 64 || a.G_N == 128)) || (a.Cout == 128 && a.G_N == 128);
-        if (!built) return false;
-    }
-    return big_eligible(a, a.Cout);
-}
-
-// the stem with the max-pool on the tile: what launch_conv_gemm needs to run `a` (pool fields set) on the sixteen-wave 512 x 64
-// tiles of the 16x16x32 split loop -- the kernel that has the pooling epilogue
-bool pooled_stem_ok(const ConvGemmArgs& a) {
-    const bool bf = a.dtype == ODAM_CG_BF16;
-    if (!g_big_mode || !(odam_cfg::get(odam_cfg::CG_TILES) & 8) || odam_cfg::get(odam_cfg::STEM_POOL) == 0) return false;
-    if (bf) {       // the sixteen-wave bf16 tiles take conv1 as a row convolution (pixel stride < row length), not a 3x3 stride 1
-        if (!(a.lda > 0 && a.lda < a.Cin) && g_big_mode < 2) return false;
-        if (a.KH * a.KW == 9 && a.stride == 1) return false;
-        if (a.out_f32) return false;
-    } else {
-        if (g_big_f32 != 2 || !a.Wt3 || odam_cfg::get(odam_cfg::CG_PRESPLIT) == 0 || odam_cfg::get(odam_cfg::CG_MFMA16) == 0) return false;
-        if (a.Kpad % 32 != 0 || (long)a.Cout * a.Kpad * 6 >= 0x7fffffffL) return false;
-    }
-    if (a.Cout != 64 || a.ldc != 64 || a.res || !a.relu) return false;
-    if (a.pool_ph != POOL_PH || a.pool_pw != POOL_PW) return false;
-    if (a.Hp != (a.Ho + 2 - 3) / 2 + 1 || a.Wp != (a.Wo + 2 - 3) / 2 + 1) return false;
-    return big_eligible(a, 64) && ((a.M + 511) / 512 >= 256 || pinned(a));
-}
-
 int launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream) {
-    const int epc = (a.dtype == ODAM_CG_BF16) ? 8 : 4;
-    if (a.Kpad % (8 * epc) != 0 || a.Cin < epc || (a.Cin & (a.Cin - 1)) != 0 || a.KW > 7 || a.KH * a.KW > 64)
-        return odam_fail(1, "conv_gemm: unsupported shape (Kpad % k-tile, Cin a power of two >= one 16-byte chunk, KW <= 7)");
-    if (a.k_order && (a.Cin % (8 * epc) != 0 || a.KH * a.KW > 32 || a.Kpad / (8 * epc) >= 2048))
-        return odam_fail(1, "conv_gemm: k_order 1 needs Cin % k-tile == 0, at most 32 taps, fewer than 2048 k-tiles");
-    if (a.M <= 0 || a.Cout <= 0) return 0;
-    if (a.pool) {
-        if (!pooled_stem_ok(a)) return odam_fail(1, "conv_gemm: pooled stem asked for where it does not apply (check pooled_stem_ok)");
-        return a.dtype == ODAM_CG_BF16 ? launch_big_bf16(64, 1024, a, stream) : launch_big_f32(4, 64, 1024, a, stream);
+    const Choice c = choose(a, current_switches());
+    if (c.family == Family::Refused) return odam_fail(c.code, c.message);
+    if (c.family == Family::Nothing) return 0;
+    char tok[PATH_TOKEN_LEN];
+    choice_token(c, tok);
+    note_path("%s", tok);
+    switch (c.family) {
+    case Family::RingF32: return launch_big_f32(c.mode, c.bn, 64 * c.waves, a, stream);
+    case Family::RingBF16: return launch_big_bf16(c.bn, 64 * c.waves, c.s1_window, a, stream);
+    case Family::FusedF32: return launch_big_fused(c.mode, a, stream);
+    case Family::FusedBF16: return launch_fused_bf16(c.s1_window, a, stream);
+    default:      // Family::Small
+        if (c.bm == 128 && c.bn == 64) return c.waves == 8 ? launch_cfg<128, 64, 4, 2>(a, c, stream) : launch_cfg<128, 64, 4, 1>(a, c, stream);
+        if (c.bm == 64) return c.stages == 4 ? launch_cfg<64, 64, 2, 2, 4>(a, c, stream) : launch_cfg<64, 64, 2, 2>(a, c, stream);
+        return c.waves == 8 ? launch_cfg<128, 128, 4, 2>(a, c, stream) : launch_cfg<128, 128, 2, 2>(a, c, stream);
     }
-    if (a.F_Wt3) {
-        if (!fused_second_ok(a)) return odam_fail(1, "conv_gemm: fused second layer asked for where it does not apply (check fused_second_ok)");
-        return launch_big_fused(a, stream);
-    }
-    if (a.F_Wt) {
-        if (!fused_bf16_ok(a)) return odam_fail(1, "conv_gemm: fused bf16 bottleneck asked for where it does not apply (check fused_bf16_ok)");
-        return launch_fused_bf16(a, stream);
-    }
-    if (g_big_mode) {
-        const bool bf = a.dtype == ODAM_CG_BF16;
-        const bool x3 = !bf && g_big_f32 == 2;
-        const bool pre = x3 && a.Wt3 != nullptr && odam_cfg::get(odam_cfg::CG_PRESPLIT) != 0 && a.Kpad % 16 == 0 && (long)a.Cout * a.Kpad * 6 < 0x7fffffffL;
-        const bool x16 = pre && odam_cfg::get(odam_cfg::CG_MFMA16) != 0 && (a.Cout & 3) == 0 && (a.ldc & 3) == 0 && a.Kpad % 32 == 0;   // 16x16x32 schedule
-        if (a.Cout % 256 == 0 || a.Cout >= 384) {
-            if (big_eligible(a, 256))
-                // bf16 plain layers (no window loop): sixteen waves of 64 x 64 (four per SIMD; 128 registers, the epilogue spills):
-                // R101 forward 17.19 -> 16.95 ms per 32 frames, the reduce layers of layer3 90 -> 87 us (same box, cg.tiles 15 vs 31)
-                return bf ? ((odam_cfg::get(odam_cfg::CG_TILES) & 16) && !(a.KH * a.KW == 9 && a.stride == 1) ? launch_big_bf16(256, 1024, a, stream) : launch_big_bf16(256, 512, a, stream))
-                          : (pre ? (x16 ? launch_big_f32(4, 256, 512, a, stream)
-                                        : launch_big_f32(3, 256, 512, a, stream)) : launch_big_f32(2, 256, 512, a, stream));
-#ifndef CG_NO_BN128_FALLBACK
-            // too few 256-wide tiles to fill the device (the encoder's N = 256 layers at M = 27,200: 107) but enough 128-wide
-            // ones: the ring kernel on 256 x 128 tiles instead of the 128 x 128 tiles of the fp32 matrix instruction
-            if (pre && big_eligible(a, 128)) return x16 ? launch_big_f32(4, 128, 512, a, stream) : launch_big_f32(3, 128, 512, a, stream);
-#endif
-        } else if (a.Cout > 64 && (g_big_mode >= 2 || x3) && big_eligible(a, 128)) {   // bf16 / fp32: measured slower than the 128x128 tiles (tests only)
-            return bf ? launch_big_bf16(128, 512, a, stream)
-                      : (pre ? (x16 ? launch_big_f32(4, 128, 512, a, stream) : launch_big_f32(3, 128, 512, a, stream)) : launch_big_f32(2, 128, 512, a, stream));
-        } else if (x3 && a.Cout > 32 && a.Cout <= 64 && big_eligible(a, 64)) {
-            // Sixteen waves on 512 x 64 tiles (cg.tiles bit 3): the 64-column loop uses ~105 registers, so FOUR waves fit a SIMD, and a
-            // wave of this loop spends more time issuing (5 DMAs of ~150 cycles, two 44-instruction splits, 28 LDS reads per 768
-            // cycles of matrix work) than the pipe needs -- with four per SIMD the pipe finds a ready wave more often, and the
-            // filter tile is fetched once per 512 rows.  conv1: 1.44 -> 1.15 ms per 32 frames (same box, A/B by config).
-            // (128-row tiles with two 4-wave workgroups per CU = the same two waves per SIMD: measured no change, not kept.)
-            if (x16 && (odam_cfg::get(odam_cfg::CG_TILES) & 8) && ((a.M + 511) / 512 >= 256 || pinned(a))) return launch_big_f32(4, 64, 1024, a, stream);      // (fewer 512-row tiles than CUs: the 256-row ones)
-            return pre ? (x16 ? launch_big_f32(4, 64, 512, a, stream) : launch_big_f32(3, 64, 512, a, stream)) : launch_big_f32(2, 64, 512, a, stream);
-        } else if (bf && (g_big_mode >= 2 || (a.lda > 0 && a.lda < a.Cin)) && a.Cout > 32 && a.Cout <= 64 && big_eligible(a, 64)) {
-            if ((odam_cfg::get(odam_cfg::CG_TILES) & 8) && !(a.KH * a.KW == 9 && a.stride == 1) && ((a.M + 511) / 512 >= 256 || pinned(a))) return launch_big_bf16(64, 1024, a, stream);
-            return launch_big_bf16(64, 512, a, stream);     // conv1 as a row convolution (pixel stride < row length); tests: layer1's 3x3 alone
-        }
-    }
-    const int variant = odam_cfg::get(odam_cfg::CG_TILES);      // 8-wave tiles (+2-3 %)
-    const int force = odam_cfg::get(odam_cfg::CG_FORCE);        // tests: pin one tile shape
-    if (force == 1) return launch_cfg<128, 64, 4, 2>(a, stream);
-    if (force == 2) return launch_cfg<64, 64, 2, 2, 4>(a, stream);
-    if (force == 3) return launch_cfg<128, 128, 2, 2>(a, stream);
-    if (a.Cout <= 64) return (variant & 2) ? launch_cfg<128, 64, 4, 2>(a, stream) : launch_cfg<128, 64, 4, 1>(a, stream);
-    const long tiles128 = (long)((a.M + 127) / 128) * ((a.Cout + 127) / 128);
-    if (tiles128 < 128) return (variant & 4) ? launch_cfg<64, 64, 2, 2, 4>(a, stream) : launch_cfg<64, 64, 2, 2>(a, stream);
-    if (variant & 1) return launch_cfg<128, 128, 4, 2>(a, stream);
-    return launch_cfg<128, 128, 2, 2>(a, stream);
 }
 
 }  // namespace odam_cg

@@ -22,7 +22,7 @@ int fail(int code, const char* who, const char* what) {
 // where the mode or the shape takes no pre-split filters; the caller frees *d3 after synchronising the stream.
 int split_filters_for_call(const float* w_packed, int Cout, int Kpad, hipStream_t st, unsigned short** d3, const char* who) {
     *d3 = nullptr;
-    if (odam_cg::f32_mode() != 2 || Kpad % 16 != 0 || (long)Cout * Kpad * 6 >= 0x7fffffffL) return 0;
+    if (!odam_cg::presplit_applies(Cout, Kpad)) return 0;
     std::vector<float> hw((size_t)Cout * Kpad);
     ODAM_HIP(hipStreamSynchronize(st));
     ODAM_HIP(hipMemcpy(hw.data(), w_packed, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -179,7 +179,7 @@ extern "C" int odam_op_conv2d_nhwc_mxfp8(const void* x, const void* xs, const vo
     return odam_mx::launch_conv(a, (hipStream_t)stream);
 }
 
-// A whole bf16 bottleneck tail as ONE launch (conv_gemm.hip fused_bf16): 3x3 (P -> P channels, stride 1 or 2, pad 1; filters
+// A whole bf16 bottleneck tail as ONE launch (cg_choice.h fused_bf16_ok, cg_fused_bf16.hip): 3x3 (P -> P channels, stride 1 or 2, pad 1; filters
 // packed k_order 1) + scale / bias / ReLU, 1x1 expand to 4 P channels + scale / bias + residual + ReLU -> y, and optionally the
 // next block's 1x1 reduce (4 P -> PN channels, scale / bias / ReLU) of y -> y_next.  Returns 4 where the fused kernel does
 // not apply to the shape (the caller then runs the layers one by one with odam_op_conv2d_nhwc_bf16; results are bit-identical).
@@ -195,7 +195,7 @@ extern "C" int odam_op_bottleneck_bf16(const void* x, const void* w2, const floa
     return odam_cg::launch_conv_gemm(a, (hipStream_t)stream);
 }
 
-// The fp32 counterpart (conv_gemm.hip fused_second_ok / launch_big_fused, split mode): 3x3 (P = 64 or 128 channels, stride 1 or 2,
+// The fp32 counterpart (cg_choice.h fused_second_ok, cg_fused_f32.hip launch_big_fused, split mode): 3x3 (P = 64 or 128 channels, stride 1 or 2,
 // pad 1; w2 [P][9 P] packed k_order 1) + scale / bias / ReLU, 1x1 expand to 4 P + scale / bias (+ residual) + ReLU -> y, and for
 // P = 64 optionally the next reduce (PN = 64 / 128) -> y_next.  The filters come packed in fp32 and are split on the host for the
 // call, as odam_op_conv2d_nhwc does.  Returns 4 where fused_second_ok refuses the shape or the configuration.
@@ -228,14 +228,14 @@ extern "C" int odam_op_bottleneck_f32(const float* x, const float* w2, const flo
 
 extern "C" long long odam_op_conv_paths(char* buf, int n, int reset) { return odam_cg::read_paths(buf, n, reset); }
 
-// experiment switch of the bf16-native contraction kernel (conv_gemm.h set_big_mode): 0 off, 1 auto, 2 whenever eligible
+// experiment switch of the bf16-native contraction kernel (cg_choice.h set_big_mode): 0 off, 1 auto, 2 whenever eligible
 extern "C" int odam_op_conv_bf16_mode(int mode) {
     if (mode < 0 || mode > 2) return odam_fail(1, "odam_op_conv_bf16_mode: mode must be 0, 1 or 2");
     odam_cg::set_big_mode(mode);      // = odam_config_set("cg.ring", mode)
     return 0;
 }
 
-// fp32 contraction mode of the 256-row kernel (conv_gemm.h set_f32_mode): 0 fp32 matrix instruction on 128x128 tiles,
+// fp32 contraction mode of the 256-row kernel (cg_choice.h set_f32_mode): 0 fp32 matrix instruction on 128x128 tiles,
 // 1 the same instruction in the ring kernel, 2 bf16 matrix instruction through the exact three-way split
 extern "C" int odam_op_conv_f32_mode(int mode) {
     if (mode != 0 && mode != 2) return odam_fail(1, "odam_op_conv_f32_mode: mode must be 0 or 2");
