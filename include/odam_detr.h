@@ -94,6 +94,23 @@ int odam_detr_forward_masked(odam_detr* m, const float* img, int B, const unsign
                              float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
                              float* obj_features, void* stream);
 
+/*
+ * The forward with the predictions of EVERY decoder layer (DETR.forward with aux_loss, detr.py:70-93, 238-253): after each
+ * decoder layer the decoder's final norm (transformer.py:117-127, in both pre_norm settings) and the six heads, on the same
+ * B * Q rows and with the same launches as the plain forward.  L = cfg.dec_layers.
+ *   key_mask, pos      as odam_detr_forward_masked, or both null for a same-size batch (odam_detr_forward)
+ *   frames_per_layer   >= B: every output pointer (obj_features nullable) addresses a block [L][frames_per_layer][Q][.], and
+ *                      layer l of frame b is written at (l * frames_per_layer + b) * Q * n -- a caller that splits a batch over
+ *                      max_batch passes the block's address advanced by its first frame and the frames of the whole block
+ *   Slot L-1 is the last layer: the bits odam_detr_forward / odam_detr_forward_masked write for the same input, in every dtype
+ *   mode.  Slots 0 .. L-2 are the reference's aux_outputs[0 .. L-2].
+ * A null pointer, a mask without a position table (or the reverse), a handle that is not finalised and frames_per_layer < B
+ * return 1 before anything is launched.  No workspace beyond the plain forward's.
+ */
+int odam_detr_forward_aux(odam_detr* m, const float* img, int B, const unsigned char* key_mask, const float* pos,
+                          float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
+                          float* obj_features, int frames_per_layer, void* stream);
+
 /* optional taps for parity tests: layer4 feature map as NCHW [B,C4,h,w] (C4 = 2048 Bottleneck, 512 BasicBlock) and encoder memory [B,h*w,hidden]
  * of the most recent forward (either may be null) */
 int odam_detr_debug_read(odam_detr* m, int B, float* layer4_nchw, float* memory, void* stream);

@@ -9,7 +9,10 @@
  *                                      loss_angle, loss_offset                                     -> odam_detr_criterion
  *   src/utils/box_utils.py:8-21, 147-166, 490-494   box_iou, generalized_box_iou, box_cxcywh_to_xyxy_pytorch (both of the above)
  *   src/utils/misc.py:415-431          accuracy (top-1)                                            -> odam_detr_criterion
- * SetCriterion.forward without aux_outputs (:441-463) is these three calls in a row (odam_amd/criterion.py).  No gradients.
+ *   src/models/detr.py:465-481         the same again for every entry of aux_outputs               -> odam_detr_match_cost_layers,
+ *                                                                                                     odam_detr_criterion_layers
+ * SetCriterion.forward without aux_outputs (:441-463) is the first three calls in a row; with aux_outputs (:465-481) the layered
+ * cost, ONE odam_lsap_batch over L B problems and the layered criterion (odam_amd/criterion.py).  No gradients.
  *
  * Conventions as in odam_sq.h: int return codes (0 = OK), odam_last_error(), [dev] / [host] pointers, stream-ordered on the
  * caller's hipStream_t, no synchronisation, no allocation, caller-owned buffers.  Plain vector stores; no floating-point
@@ -71,6 +74,18 @@
  *   out_status   [dev] int32 [B]
  *   B >= 1 (F.cross_entropy of no query is NaN and the reference's mean over no frame too: ODAM_E_INVALID), Q >= 0,
  *   n_logit >= 2, n_angle >= 1, W >= 12.
+ *
+ * odam_detr_match_cost_layers, odam_detr_criterion_layers -- the two entries above with a leading layer dimension L >= 1 on every
+ * prediction tensor ([L][B][Q][.], e.g. the blocks odam_detr_forward_aux fills); the targets of frame b serve every layer.
+ *   cost_out     [dev] float32 [L][Q * n_obj]: layer l's frame b at l Q n_obj + Q obj_off[b]
+ *   match        [dev] int32 [L][B][Q]   (odam_lsap_batch over the L B problems with match_off[l B + b] = (l B + b) Q)
+ *   out_partial  [dev] float64 [L][B][ODAM_LOSS_N_PARTIAL]     out_table [dev] float64 [L][ODAM_LOSS_N_ENTRIES]
+ *   out_status   [dev] int32 [L][B]   (both entries)
+ * The cost is ONE launch, one workgroup per (layer, frame); the criterion TWO, one wavefront per (layer, frame), then one per
+ * layer.  The kernels are instantiations of the single-layer ones with the layer in a further grid dimension: layer l of a layered
+ * call holds the bits of the single-layer call on that layer's tensors (cost block, partial sums, table, status), wherever the
+ * layer stands and whatever L is.  L < 1 is ODAM_E_INVALID (more than 65535 layers ODAM_E_LIMIT); every other argument is checked
+ * as by the single-layer entry, before anything is launched.
  */
 #ifndef ODAM_LOSS_H
 #define ODAM_LOSS_H
@@ -101,6 +116,15 @@ int odam_detr_criterion(const float* logits, const float* boxes, const float* an
                         const float* depth, int B, int Q, int n_logit, int n_angle, const float* objects, const int* obj_off,
                         int n_obj, int W, const int* match, double num_boxes, float eos_coef, const double* weights,
                         double* out_partial, double* out_table, int* out_status, void* stream);
+
+int odam_detr_match_cost_layers(const float* logits, const float* boxes, int L, int B, int Q, int n_logit, const float* objects,
+                                const int* obj_off, int n_obj, int W, float cost_class, float cost_bbox, float cost_giou,
+                                float* cost_out, int* out_status, void* stream);
+
+int odam_detr_criterion_layers(const float* logits, const float* boxes, const float* angle, const float* offset, const float* size,
+                               const float* depth, int L, int B, int Q, int n_logit, int n_angle, const float* objects,
+                               const int* obj_off, int n_obj, int W, const int* match, double num_boxes, float eos_coef,
+                               const double* weights, double* out_partial, double* out_table, int* out_status, void* stream);
 
 #ifdef __cplusplus
 }

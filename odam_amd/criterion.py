@@ -1,6 +1,7 @@
 """The detector's validation loss on the device: the reference's HungarianMatcher (src/models/matcher.py:11-82) and SetCriterion
-(src/models/detr.py:258-481, without aux_outputs, masks and gradients) under their own names and argument order, over the three
-entry points of include/odam_loss.h (csrc/det_loss.hip).
+(src/models/detr.py:258-481, without masks and gradients) under their own names and argument order, over the entry points of
+include/odam_loss.h (csrc/det_loss.hip).  With "aux_outputs" among the outputs (Detector(..., aux=True)) every decoder layer is
+matched and scored in the same few launches, and the total is the one of the model's training log (build(cfg) with aux_loss).
 
     criterion = odam_amd.criterion.build(cfg)                  # or SetCriterion(num_classes, HungarianMatcher(...), weight_dict, eos_coef, losses)
     losses = criterion(det(frames), targets)                   # {"loss_ce": 0-d tensor, "class_error": ..., ...}
@@ -38,6 +39,8 @@ LOSS_ARGTYPES = {
     "odam_detr_match_cost": [_P, _P, _I, _I, _I, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P],
     "odam_lsap_batch": [_P, _L, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "odam_detr_criterion": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _D, _F, _P, _P, _P, _P, _P],
+    "odam_detr_match_cost_layers": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P],
+    "odam_detr_criterion_layers": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _D, _F, _P, _P, _P, _P, _P],
 }
 _OUT_KEYS = ("pred_logits", "pred_boxes", "pred_angle", "pred_offset", "pred_size", "pred_depth")
 _OUT_LAST = {"pred_boxes": 4, "pred_offset": 2, "pred_size": 3, "pred_depth": 1}
@@ -112,6 +115,55 @@ def _raise_for_status(words, what):
         raise IndexError(f"{what}: a target label or angle bin is outside the classes of the output")
     if st & ST_DEGENERATE:
         raise AssertionError(f"{what}: a box with x1 < x0 or y1 < y0 (generalized_box_iou refuses degenerate boxes)")
+
+
+class DegenerateBoxError(AssertionError, ValueError):
+    """a degenerate box met while every decoder layer is scored: the reference's AssertionError (generalized_box_iou), which is
+    also a ValueError about the batch handed in -- it names the layers and frames"""
+
+
+def _raise_for_status_layers(words, what):
+    """_raise_for_status for status words [L, B] of a layered call: the exception names every (layer, frame) that set the bit"""
+    words = np.asarray(words, np.int64)
+    st = int(np.bitwise_or.reduce(words.reshape(-1), initial=0))
+    if not st:
+        return
+    L = words.shape[0]
+
+    def where(bit):
+        return "; ".join("layer %d%s: frame%s %s" % (l, " (last)" if l == L - 1 else "", "s" if np.count_nonzero(words[l] & bit) > 1 else "",
+                                                      ", ".join(str(b) for b in np.nonzero(words[l] & bit)[0]))
+                         for l in range(L) if (words[l] & bit).any())
+    if st & ST_OFFSETS:
+        raise _lib.OdamError(f"{what}: target offsets or assignment indices outside their frame ({where(ST_OFFSETS)})")
+    if st & ST_CLASS:
+        raise IndexError(f"{what}: a target label or angle bin is outside the classes of the output ({where(ST_CLASS)})")
+    raise DegenerateBoxError(f"{what}: a box with x1 < x0 or y1 < y0 (generalized_box_iou refuses degenerate boxes) "
+                             f"({where(ST_DEGENERATE)})")
+
+
+def _layer_block(tensors):
+    """[L] tensors of one shape (device, float32, contiguous) -> one [L, ...] tensor: the view over them when they already lie one
+    after the other in one allocation (the blocks of Detector(..., aux=True)), else a stacked copy"""
+    first, n = tensors[0], tensors[0].numel()
+    if n and all(t.untyped_storage().data_ptr() == first.untyped_storage().data_ptr() and
+                 t.data_ptr() == first.data_ptr() + 4 * n * l for l, t in enumerate(tensors)):
+        return first.as_strided((len(tensors),) + tuple(first.shape), (n,) + tuple(first.stride()))
+    return torch.stack(tensors).contiguous()
+
+
+def match_cost_layers(S, logits, boxes, cost_class, cost_bbox, cost_giou):
+    """odam_detr_match_cost_layers on logits / boxes [L, B, Q, .] and the staged targets S -> (cost float32 [L, Q * n_obj] -- one
+    word per layer when no frame has a target -- and status int32 [L, B], both on the device)"""
+    L = int(logits.shape[0])
+    cost = torch.empty(L, max(S.Q * S.n_obj, 1), device=S.dev, dtype=torch.float32)
+    status = torch.empty(L, max(S.B, 1), device=S.dev, dtype=torch.int32)
+    with torch.cuda.device(S.dev):
+        _lib.check(_entry("odam_detr_match_cost_layers")(
+            _lib.ptr(logits), _lib.ptr(boxes), L, S.B, S.Q, S.n_logit, _lib.ptr(S.objects), _lib.ptr(S.d_off), S.n_obj, S.W,
+            float(cost_class), float(cost_bbox), float(cost_giou), _lib.ptr(cost), _lib.ptr(status), _stream(S.dev)),
+            "odam_detr_match_cost_layers")
+    return cost, status[:, :S.B]
 
 
 def match_cost(S, cost_class, cost_bbox, cost_giou):
@@ -226,6 +278,19 @@ class HungarianMatcher:
         col, st, _ = solve(cost, [(S.Q, g) for g in S.sizes], S.Q * S.off[:-1], S.dev)
         return col.view(S.B, S.Q), [st_cost] + ([st] if st is not None else [])
 
+    def assign_layers(self, S, logits, boxes):
+        """`assign` for logits / boxes [L, B, Q, .] of every decoder layer against the staged targets S: ONE cost launch and ONE
+        solver launch over the L B problems -> (match int32 [L, B, Q], [cost status [L, B], solver status [L B]] on the device).
+        The solver's limits and the host's scipy for a frame beyond them hold per problem, as in `assign`."""
+        L = int(logits.shape[0])
+        cost, st_cost = match_cost_layers(S, logits, boxes, self.cost_class, self.cost_bbox, self.cost_giou)
+        if any(min(S.Q, g) > LSAP_MAX_SMALL or max(S.Q, g) > LSAP_MAX_LARGE for g in S.sizes):
+            _raise_for_status_layers(st_cost.cpu().numpy(), "HungarianMatcher")      # before scipy reads a block that may hold no meaning
+        per_layer = S.Q * S.n_obj
+        off = np.concatenate([l * per_layer + S.Q * S.off[:-1] for l in range(L)])
+        col, st, _ = solve(cost, [(S.Q, g) for g in S.sizes] * L, off, S.dev)
+        return col.view(L, S.B, S.Q), [st_cost] + ([st] if st is not None else [])
+
     def __call__(self, outputs, targets):
         S = _Staged(outputs, targets, keys=("pred_logits", "pred_boxes"))
         match, words = self.assign(S)
@@ -239,11 +304,14 @@ class HungarianMatcher:
 
 
 class SetCriterion:
-    """detr.py:258-481 without aux_outputs: criterion(outputs, targets) -> {key: 0-d float64 CPU tensor} under the reference's
-    keys, for the requested `losses` (any of LOSS_NAMES; 'masks' is refused).  `matcher` is a HungarianMatcher of this module (the
-    assignment then never leaves the device) or any callable returning the reference's list of (index_i, index_j).
+    """detr.py:258-481: criterion(outputs, targets) -> {key: 0-d float64 CPU tensor} under the reference's keys, for the requested
+    `losses` (any of LOSS_NAMES; 'masks' is refused).  `matcher` is a HungarianMatcher of this module (the assignment then never
+    leaves the device) or any callable returning the reference's list of (index_i, index_j).  When `outputs` holds a non-empty
+    "aux_outputs" (Detector(..., aux=True), or the reference's list of dicts) every decoder layer is matched and scored as well, under
+    "loss_*_{i}" and "cardinality_error_{i}" (no "class_error_{i}": the reference's log=False), with the call's num_boxes.
     After a call `last_partial` holds the per-frame partial sums [B, 11] (PARTIAL_KEYS) and `last_table` the whole table
-    (TABLE_KEYS, with "total" over the weights of the requested losses), both on the device."""
+    (TABLE_KEYS, with "total" over the weights of the requested losses) of the LAST layer, `last_partial_layers` [L, B, 11] and
+    `last_table_layers` [L, 10] those of every layer in decoder order (L = 1 without aux_outputs), all on the device."""
 
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses):
         losses = list(losses)
@@ -253,21 +321,96 @@ class SetCriterion:
             if name not in LOSS_NAMES:
                 raise ValueError(f"do you really want to compute {name} loss? (one of {', '.join(LOSS_NAMES)})")
         self.num_classes, self.matcher, self.weight_dict, self.eos_coef, self.losses = num_classes, matcher, dict(weight_dict), eos_coef, losses
-        self.last_partial = self.last_table = None
+        self.last_partial = self.last_table = self.last_partial_layers = self.last_table_layers = None
 
     def _weights(self):
         want = {k for name in self.losses for k in KEYS_OF_LOSS[name]}
         return [float(self.weight_dict.get(k, 0.0)) if k in want else 0.0 for k in WEIGHT_KEYS]
 
     def total(self, losses):
-        """sum(losses[k] * weight_dict[k]) over the keys both have, added in the order of WEIGHT_KEYS (the kernel's order)"""
+        """sum(losses[k] * weight_dict[k]) over the keys both have, added in the order of WEIGHT_KEYS (the kernel's order); then
+        the keys of the decoder layers 0, 1, ... ("loss_ce_0", ...), each layer in the order of WEIGHT_KEYS"""
         tot = 0.0
         for k in WEIGHT_KEYS:
             if k in losses and k in self.weight_dict and float(self.weight_dict[k]) != 0.0:
                 tot = tot + float(self.weight_dict[k]) * losses[k]
+        layers = sorted({int(k.rsplit("_", 1)[1]) for k in losses
+                         if isinstance(k, str) and k.rsplit("_", 1)[-1].isdigit() and k.rsplit("_", 1)[0] in WEIGHT_KEYS})
+        for i in layers:
+            for base in WEIGHT_KEYS:
+                k = f"{base}_{i}"
+                if k in losses and k in self.weight_dict and float(self.weight_dict[k]) != 0.0:
+                    tot = tot + float(self.weight_dict[k]) * losses[k]
         return torch.as_tensor(tot, dtype=torch.float64)
 
+    def _call_layers(self, outputs, targets, num_boxes):
+        """detr.py:441-481 with aux_outputs: the last layer and every entry of outputs["aux_outputs"], as ONE layered cost launch,
+        ONE solver launch, the TWO layered criterion launches and one copy to the host.  The layers go to the kernels in decoder
+        order (aux_outputs[0] first, the last layer in slot L-1); the "total" entry of every layer's table is formed with the
+        weights of the unsuffixed keys."""
+        last = {k: v for k, v in outputs.items() if k != "aux_outputs"}
+        layers = list(outputs["aux_outputs"]) + [last]
+        L = len(layers)
+        S = _Staged(last, targets)
+        if S.n_logit != self.num_classes + 1:
+            raise ValueError(f"pred_logits have {S.n_logit} columns, the criterion was built for {self.num_classes} classes + no-object")
+        if S.B < 1:
+            raise ValueError("the criterion needs at least one frame")
+        blk = {}
+        for k in _OUT_KEYS:
+            ts = []
+            for i, d in enumerate(layers[:-1]):
+                if k not in d:
+                    raise KeyError(f"aux_outputs[{i}] has no {k!r}")
+                if tuple(d[k].shape) != tuple(S.t[k].shape):
+                    raise ValueError(f"aux_outputs[{i}][{k!r}] must be {list(S.t[k].shape)}, got {list(d[k].shape)}")
+                ts.append(_f32(d[k], S.dev))
+            blk[k] = _layer_block(ts + [S.t[k]])
+        if isinstance(self.matcher, HungarianMatcher):
+            match, words = self.matcher.assign_layers(S, blk["pred_logits"], blk["pred_boxes"])
+        else:      # a caller's matcher: once per layer, as the reference calls it
+            m = np.full((L, S.B, S.Q), -1, np.int32)
+            for l, d in enumerate(layers):
+                for b, (i, j) in enumerate(self.matcher(d, targets)):
+                    m[l, b, np.asarray(i, np.int64)] = np.asarray(j, np.int64)
+            match, words = torch.from_numpy(m).to(S.dev), []
+        if num_boxes is None:
+            num_boxes = max(S.n_obj, 1)
+        n_ent, n_part = len(TABLE_KEYS), len(PARTIAL_KEYS)
+        partial = torch.empty(L, S.B, n_part, device=S.dev, dtype=torch.float64)
+        table = torch.empty(L, n_ent, device=S.dev, dtype=torch.float64)
+        status = torch.empty(L, S.B, device=S.dev, dtype=torch.int32)
+        w = (ctypes.c_double * len(WEIGHT_KEYS))(*self._weights())
+        match = match.contiguous()
+        with torch.cuda.device(S.dev):
+            _lib.check(_entry("odam_detr_criterion_layers")(
+                _lib.ptr(blk["pred_logits"]), _lib.ptr(blk["pred_boxes"]), _lib.ptr(blk["pred_angle"]), _lib.ptr(blk["pred_offset"]),
+                _lib.ptr(blk["pred_size"]), _lib.ptr(blk["pred_depth"]), L, S.B, S.Q, S.n_logit, int(S.t["pred_angle"].shape[2]),
+                _lib.ptr(S.objects), _lib.ptr(S.d_off), S.n_obj, S.W, _lib.ptr(match), float(num_boxes), float(self.eos_coef),
+                ctypes.cast(w, ctypes.c_void_p), _lib.ptr(partial), _lib.ptr(table), _lib.ptr(status), _stream(S.dev)),
+                "odam_detr_criterion_layers")
+        # the one copy to the host: every layer's table and, behind them, the status words of the three calls
+        tail = [x.reshape(-1).to(torch.float64) for x in words] + [status.reshape(-1).to(torch.float64)]
+        host = torch.cat([table.reshape(-1)] + tail).cpu().numpy()
+        lens = [len(x) for x in tail]
+        st = np.split(host[L * n_ent:].astype(np.int64), np.cumsum(lens)[:-1])
+        if words:
+            _raise_for_status_layers(st[0].reshape(L, S.B), "SetCriterion (matcher)")
+            if len(words) > 1 and st[1].any():
+                raise ValueError("SetCriterion: cost matrix is infeasible or contains invalid numeric entries")
+        _raise_for_status_layers(st[-1].reshape(L, S.B), "SetCriterion")
+        self.last_partial_layers, self.last_table_layers = partial, table
+        self.last_partial, self.last_table = partial[L - 1], table[L - 1]
+        vals = host[:L * n_ent].reshape(L, n_ent)
+        res = {k: torch.as_tensor(vals[L - 1][TABLE_KEYS.index(k)], dtype=torch.float64) for name in self.losses for k in KEYS_OF_LOSS[name]}
+        for i in range(L - 1):      # the reference's log=False: no class_error of an aux layer
+            res.update({f"{k}_{i}": torch.as_tensor(vals[i][TABLE_KEYS.index(k)], dtype=torch.float64)
+                        for name in self.losses for k in KEYS_OF_LOSS[name] if k != "class_error"})
+        return res
+
     def __call__(self, outputs, targets, num_boxes=None):
+        if outputs.get("aux_outputs"):
+            return self._call_layers(outputs, targets, num_boxes)
         S = _Staged(outputs, targets)
         if S.n_logit != self.num_classes + 1:
             raise ValueError(f"pred_logits have {S.n_logit} columns, the criterion was built for {self.num_classes} classes + no-object")
@@ -307,6 +450,7 @@ class SetCriterion:
                 raise ValueError("SetCriterion: cost matrix is infeasible or contains invalid numeric entries")
         _raise_for_status(st[-1], "SetCriterion")
         self.last_partial, self.last_table = partial, table
+        self.last_partial_layers, self.last_table_layers = partial[None], table[None]
         vals = dict(zip(TABLE_KEYS, host[:n_ent]))
         return {k: torch.as_tensor(vals[k], dtype=torch.float64) for name in self.losses for k in KEYS_OF_LOSS[name]}
 
@@ -315,7 +459,8 @@ class SetCriterion:
 
 def build(args):
     """the criterion of detr.py:530-565 `build(args)` (its second return value) from the same keys: set_cost_class, set_cost_bbox,
-    set_cost_giou (build_matcher), bbox_loss_coef, giou_loss_coef, eos_coef, dataset_file.  `args` is a namespace or a dict."""
+    set_cost_giou (build_matcher), bbox_loss_coef, giou_loss_coef, eos_coef, dataset_file, and -- with a truthy aux_loss -- dec_layers:
+    every weight again under "{key}_{i}" for the dec_layers - 1 aux layers (:556-560).  `args` is a namespace or a dict."""
     if isinstance(args, dict):
         g, has = args.__getitem__, args.__contains__
     else:
@@ -327,4 +472,9 @@ def build(args):
     matcher = HungarianMatcher(cost_class=g("set_cost_class"), cost_bbox=g("set_cost_bbox"), cost_giou=g("set_cost_giou"))
     weight_dict = {"loss_ce": 1, "loss_bbox": g("bbox_loss_coef"), "loss_angle": 1, "loss_offset": 3, "loss_size": 1, "loss_depth": 1}
     weight_dict["loss_giou"] = g("giou_loss_coef")
+    if has("aux_loss") and g("aux_loss"):
+        aux_weight_dict = {}
+        for i in range(g("dec_layers") - 1):
+            aux_weight_dict.update({k + f"_{i}": v for k, v in weight_dict.items()})
+        weight_dict.update(aux_weight_dict)
     return SetCriterion(num_classes, matcher=matcher, weight_dict=weight_dict, eos_coef=g("eos_coef"), losses=list(LOSS_NAMES))

@@ -1,7 +1,8 @@
 // det_loss.hip -- the detector's validation loss on the device (include/odam_loss.h): the matcher's cost matrix, the assignment
 // of every frame and the losses under it -- the reference's HungarianMatcher (likojack/ODAM src/models/matcher.py:11-82) and
-// SetCriterion (src/models/detr.py:258-481, last decoder layer only).  Arithmetic in det_loss_core.h; restated in numpy by
-// tests/criterion_ref.py.
+// SetCriterion (src/models/detr.py:258-481; one decoder layer per call, or all of them through the *_layers entries, whose
+// kernels are the <true> instantiations of the same templates with the layer in one more grid dimension).  Arithmetic in
+// det_loss_core.h; restated in numpy by tests/criterion_ref.py.
 //
 // Four small kernels, each running to completion on its own:
 //   match_cost_kernel       one workgroup per frame, lanes over queries.  A lane keeps its query's box, its corners and the maximum
@@ -57,7 +58,14 @@ struct CostArgs {
     float* out; int* status;
 };
 
-__global__ __launch_bounds__(COST_BLOCK) void match_cost_kernel(CostArgs K) {
+// LAYERS: [L][B][Q][.] predictions, grid (B, L) -- workgroup (b, l) is frame b of the single-layer call on layer l's tensors, cost
+// blocks and status words.  The <false> instantiation is the kernel as it was
+template <bool LAYERS> __global__ __launch_bounds__(COST_BLOCK) void match_cost_kernel(CostArgs K) {
+    if constexpr (LAYERS) {
+        const size_t l = blockIdx.y, rows = l * (size_t)K.B * K.Q;
+        K.logits += rows * K.n_logit; K.boxes += rows * 4;
+        K.out += l * (size_t)K.Q * K.n_obj; K.status += l * (size_t)K.B;
+    }
     __shared__ float s_box[STAGE][4], s_xy[STAGE][4];
     __shared__ int s_lab[STAGE];
     __shared__ int s_flag;
@@ -257,7 +265,18 @@ struct CritArgs {
     double* partial; double* table; int* status;
 };
 
-__global__ __launch_bounds__(64) void criterion_frame_kernel(CritArgs K) {
+// layer l of [L][B][Q][.] predictions, match [L][B][Q], partial [L][B][11], table [L][10], status [L][B]: the single-layer call on
+// that layer's words
+__device__ __forceinline__ void crit_layer(CritArgs& K, const size_t l) {
+    const size_t frames = l * (size_t)K.B, rows = frames * K.Q;
+    K.logits += rows * K.n_logit; K.boxes += rows * 4; K.angle += rows * K.n_angle; K.offset += rows * 2; K.size += rows * 3;
+    K.depth += rows; K.match += rows;
+    K.partial += frames * N_PART; K.table += l * N_ENT; K.status += frames;
+}
+
+// LAYERS: grid (B, L), one wavefront per (frame, layer).  The <false> instantiation is the kernel as it was
+template <bool LAYERS> __global__ __launch_bounds__(64) void criterion_frame_kernel(CritArgs K) {
+    if constexpr (LAYERS) crit_layer(K, blockIdx.y);
     const int b = blockIdx.x, lane = threadIdx.x;
     double* part = K.partial + (size_t)b * N_PART;
     const int g0 = K.obj_off[b], g1 = K.obj_off[b + 1];
@@ -326,7 +345,9 @@ __global__ __launch_bounds__(64) void criterion_frame_kernel(CritArgs K) {
     }
 }
 
-__global__ __launch_bounds__(64) void criterion_table_kernel(CritArgs K) {
+// LAYERS: grid (L), one wavefront per layer.  The <false> instantiation is the kernel as it was
+template <bool LAYERS> __global__ __launch_bounds__(64) void criterion_table_kernel(CritArgs K) {
+    if constexpr (LAYERS) crit_layer(K, blockIdx.x);
     __shared__ double S[N_PART];
     const int lane = threadIdx.x;
     if (lane < N_PART) {
@@ -351,6 +372,23 @@ __global__ __launch_bounds__(64) void criterion_table_kernel(CritArgs K) {
 
 }  // namespace
 
+extern "C" int odam_detr_match_cost_layers(const float* logits, const float* boxes, int L, int B, int Q, int n_logit,
+                                           const float* objects, const int* obj_off, int n_obj, int W, float cost_class,
+                                           float cost_bbox, float cost_giou, float* cost_out, int* out_status, void* stream) {
+    if (L < 1) return odam_fail(ODAM_E_INVALID, "odam_detr_match_cost_layers: at least one layer");
+    if (L > 65535) return odam_fail(ODAM_E_LIMIT, "odam_detr_match_cost_layers: more than 65535 layers");
+    if (B < 0 || Q < 0 || n_obj < 0) return odam_fail(ODAM_E_INVALID, "odam_detr_match_cost_layers: bad size");
+    if (n_logit < 2) return odam_fail(ODAM_E_INVALID, "odam_detr_match_cost_layers: n_logit below 2 (classes and the no-object column)");
+    if (W < 12) return odam_fail(ODAM_E_INVALID, "odam_detr_match_cost_layers: target rows need W >= 12");
+    if (!logits || !boxes || !objects || !obj_off || !cost_out || !out_status)
+        return odam_fail(ODAM_E_INVALID, "odam_detr_match_cost_layers: null pointer");
+    if (B == 0) return ODAM_OK;
+    CostArgs K{logits, boxes, objects, obj_off, B, Q, n_logit, n_obj, W, cost_class, cost_bbox, cost_giou, cost_out, out_status};
+    hipLaunchKernelGGL(match_cost_kernel<true>, dim3((unsigned)B, (unsigned)L), dim3(COST_BLOCK), 0, (hipStream_t)stream, K);
+    ODAM_HIP(hipGetLastError());
+    return ODAM_OK;
+}
+
 extern "C" int odam_detr_match_cost(const float* logits, const float* boxes, int B, int Q, int n_logit, const float* objects,
                                     const int* obj_off, int n_obj, int W, float cost_class, float cost_bbox, float cost_giou,
                                     float* cost_out, int* out_status, void* stream) {
@@ -360,7 +398,7 @@ extern "C" int odam_detr_match_cost(const float* logits, const float* boxes, int
     if (!logits || !boxes || !objects || !obj_off || !cost_out || !out_status) return odam_fail(ODAM_E_INVALID, "odam_detr_match_cost: null pointer");
     if (B == 0) return ODAM_OK;
     CostArgs K{logits, boxes, objects, obj_off, B, Q, n_logit, n_obj, W, cost_class, cost_bbox, cost_giou, cost_out, out_status};
-    hipLaunchKernelGGL(match_cost_kernel, dim3((unsigned)B), dim3(COST_BLOCK), 0, (hipStream_t)stream, K);
+    hipLaunchKernelGGL(match_cost_kernel<false>, dim3((unsigned)B), dim3(COST_BLOCK), 0, (hipStream_t)stream, K);
     ODAM_HIP(hipGetLastError());
     return ODAM_OK;
 }
@@ -397,8 +435,34 @@ extern "C" int odam_detr_criterion(const float* logits, const float* boxes, cons
     K.eos = eos_coef; K.num_boxes = num_boxes;
     for (int k = 0; k < N_W; k++) K.w[k] = weights[k];
     K.partial = out_partial; K.table = out_table; K.status = out_status;
-    hipLaunchKernelGGL(criterion_frame_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, K);
-    hipLaunchKernelGGL(criterion_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
+    hipLaunchKernelGGL(criterion_frame_kernel<false>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, K);
+    hipLaunchKernelGGL(criterion_table_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
+    ODAM_HIP(hipGetLastError());
+    return ODAM_OK;
+}
+
+extern "C" int odam_detr_criterion_layers(const float* logits, const float* boxes, const float* angle, const float* offset,
+                                          const float* size, const float* depth, int L, int B, int Q, int n_logit, int n_angle,
+                                          const float* objects, const int* obj_off, int n_obj, int W, const int* match,
+                                          double num_boxes, float eos_coef, const double* weights, double* out_partial,
+                                          double* out_table, int* out_status, void* stream) {
+    if (L < 1) return odam_fail(ODAM_E_INVALID, "odam_detr_criterion_layers: at least one layer");
+    if (L > 65535) return odam_fail(ODAM_E_LIMIT, "odam_detr_criterion_layers: more than 65535 layers");
+    if (B < 1 || Q < 0 || n_obj < 0) return odam_fail(ODAM_E_INVALID, "odam_detr_criterion_layers: bad size (at least one frame)");
+    if (n_logit < 2 || n_angle < 1) return odam_fail(ODAM_E_INVALID, "odam_detr_criterion_layers: n_logit below 2 or n_angle below 1");
+    if (W < 12) return odam_fail(ODAM_E_INVALID, "odam_detr_criterion_layers: target rows need W >= 12");
+    if (!(num_boxes > 0.0)) return odam_fail(ODAM_E_INVALID, "odam_detr_criterion_layers: num_boxes must be positive");
+    if (!logits || !boxes || !angle || !offset || !size || !depth || !objects || !obj_off || !match || !weights || !out_partial ||
+        !out_table || !out_status)
+        return odam_fail(ODAM_E_INVALID, "odam_detr_criterion_layers: null pointer");
+    CritArgs K{};
+    K.logits = logits; K.boxes = boxes; K.angle = angle; K.offset = offset; K.size = size; K.depth = depth; K.objects = objects;
+    K.obj_off = obj_off; K.match = match; K.B = B; K.Q = Q; K.n_logit = n_logit; K.n_angle = n_angle; K.n_obj = n_obj; K.W = W;
+    K.eos = eos_coef; K.num_boxes = num_boxes;
+    for (int k = 0; k < N_W; k++) K.w[k] = weights[k];
+    K.partial = out_partial; K.table = out_table; K.status = out_status;
+    hipLaunchKernelGGL(criterion_frame_kernel<true>, dim3((unsigned)B, (unsigned)L), dim3(64), 0, (hipStream_t)stream, K);
+    hipLaunchKernelGGL(criterion_table_kernel<true>, dim3((unsigned)L), dim3(64), 0, (hipStream_t)stream, K);
     ODAM_HIP(hipGetLastError());
     return ODAM_OK;
 }

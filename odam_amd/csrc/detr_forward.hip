@@ -297,8 +297,38 @@ int encoder(odam_detr* m, int B, const float* pos, int Lp, const unsigned char* 
     return 0;
 }
 
-// decoder layers (transformer.py:217-262) over the stacked cross-attention keys / values kc / vc; leaves their output in tgt
-int decoder(odam_detr* m, int B, const unsigned char* key_mask, hipStream_t st) {
+// the decoder's final norm (transformer.py:120-121) and the heads on its output (detr.py:73-88), fp32 in every mode
+int heads(odam_detr* m, int B, float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
+          float* obj_features, hipStream_t st) {
+    const int E = m->cfg.hidden_dim, Q = m->cfg.num_queries, dt = m->dt, Mq = B * Q;
+    // fp32 mode: the final norm can write straight into the caller's obj_features buffer
+    void* hs = (obj_features && dt == 0) ? (void*)obj_features : (void*)m->hs;
+    RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, m->dec_norm.g, m->dec_norm.b, hs, nullptr, Q, nullptr, Mq, dt, st, E));
+    if (obj_features && dt != 0) RC(odam_dk::launch_to_f32(m->hs, obj_features, (size_t)Mq * E, dt, st));
+    RC(lin_t(m, m->class_embed, hs, Mq, nullptr, false, logits, st, 1));
+    float* outs[5] = {boxes, offset, angle, size, depth};
+    for (int k = 0; k < 5; k++) {
+        RC(lin_t(m, m->mlp[k][0], hs, Mq, nullptr, true, m->h1, st));
+        RC(lin_t(m, m->mlp[k][1], m->h1, Mq, nullptr, true, m->h2, st));
+        RC(lin_t(m, m->mlp[k][2], m->h2, Mq, nullptr, false, outs[k], st, 1));
+    }
+    return odam_dk::launch_sigmoid(boxes, Mq * 4, st);
+}
+
+// where odam_detr_forward_aux puts every decoder layer's outputs: blocks [L][fpl][Q][.], layer l of frame b at (l * fpl + b) * Q * n
+struct LayerOut { float *logits, *boxes, *angle, *offset, *size, *depth, *obj_features; int fpl; };
+
+// norm + heads of decoder layer l (transformer.py:117-118: every intermediate goes through the decoder's final norm) into slot l:
+// heads() as it stands, on the same B * Q rows, so that slot L-1 holds the bits of the plain forward
+int layer_heads(odam_detr* m, int B, const LayerOut& o, size_t l, hipStream_t st) {
+    const size_t row = l * (size_t)o.fpl * m->cfg.num_queries;
+    return heads(m, B, o.logits + row * m->cfg.num_classes1, o.boxes + row * 4, o.angle + row * m->cfg.angle_bins, o.offset + row * 2,
+                 o.size + row * 3, o.depth + row, o.obj_features ? o.obj_features + row * m->cfg.hidden_dim : nullptr, st);
+}
+
+// decoder layers (transformer.py:217-262) over the stacked cross-attention keys / values kc / vc; leaves their output in tgt.
+// `each` (nullable): the heads run after every layer into that layer's slot (hs / h1 / h2 are no layer's own: reused on the one stream)
+int decoder(odam_detr* m, int B, const unsigned char* key_mask, hipStream_t st, const LayerOut* each = nullptr) {
     const int E = m->cfg.hidden_dim, Hh = m->cfg.nheads, Q = m->cfg.num_queries, dt = m->dt, L = m->L, Mq = B * Q;
     ODAM_HIP(hipMemsetAsync(m->tgt, 0, (size_t)m->es * Mq * E, st));
     RC(odam_dk::launch_add_pos(nullptr, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
@@ -319,6 +349,7 @@ int decoder(odam_detr* m, int B, const unsigned char* key_mask, hipStream_t st) 
             RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, d.n3.g, d.n3.b, m->dtmp, nullptr, Q, nullptr, Mq, dt, st, E));
             RC(lin_t(m, d.l1, m->dtmp, Mq, nullptr, true, m->dffn, st));
             RC(lin_t(m, d.l2, m->dffn, Mq, m->tgt, false, m->tgt, st));
+            if (each) RC(layer_heads(m, B, *each, i, st));
             continue;
         }
         RC(lin_t(m, d.qk, m->tgtpos, Mq, nullptr, false, m->dqk, st));
@@ -333,26 +364,9 @@ int decoder(odam_detr* m, int B, const unsigned char* key_mask, hipStream_t st) 
         RC(lin_t(m, d.l1, m->tgt, Mq, nullptr, true, m->dffn, st));
         RC(lin_t(m, d.l2, m->dffn, Mq, m->tgt, false, m->dtmp, st));
         RC(odam_dk::launch_add_layernorm(m->dtmp, nullptr, d.n3.g, d.n3.b, m->tgt, m->query_pos, Q, m->tgtpos, Mq, dt, st, E));
+        if (each) RC(layer_heads(m, B, *each, i, st));
     }
     return 0;
-}
-
-// the decoder's final norm (transformer.py:120-121) and the heads on its output (detr.py:73-88), fp32 in every mode
-int heads(odam_detr* m, int B, float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
-          float* obj_features, hipStream_t st) {
-    const int E = m->cfg.hidden_dim, Q = m->cfg.num_queries, dt = m->dt, Mq = B * Q;
-    // fp32 mode: the final norm can write straight into the caller's obj_features buffer
-    void* hs = (obj_features && dt == 0) ? (void*)obj_features : (void*)m->hs;
-    RC(odam_dk::launch_add_layernorm(m->tgt, nullptr, m->dec_norm.g, m->dec_norm.b, hs, nullptr, Q, nullptr, Mq, dt, st, E));
-    if (obj_features && dt != 0) RC(odam_dk::launch_to_f32(m->hs, obj_features, (size_t)Mq * E, dt, st));
-    RC(lin_t(m, m->class_embed, hs, Mq, nullptr, false, logits, st, 1));
-    float* outs[5] = {boxes, offset, angle, size, depth};
-    for (int k = 0; k < 5; k++) {
-        RC(lin_t(m, m->mlp[k][0], hs, Mq, nullptr, true, m->h1, st));
-        RC(lin_t(m, m->mlp[k][1], m->h1, Mq, nullptr, true, m->h2, st));
-        RC(lin_t(m, m->mlp[k][2], m->h2, Mq, nullptr, false, outs[k], st, 1));
-    }
-    return odam_dk::launch_sigmoid(boxes, Mq * 4, st);
 }
 
 // key_mask / pos_b: null for same-size batches (no padding: the mask is all false and one position table serves every
@@ -360,7 +374,7 @@ int heads(odam_detr* m, int B, float* logits, float* boxes, float* angle, float*
 // embedding, which depends on its mask (position_encoding.py:26-46).
 int forward_impl(odam_detr* m, const float* img, int B, const unsigned char* key_mask, const float* pos_b,
                  float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
-                 float* obj_features, void* stream) {
+                 float* obj_features, void* stream, int frames_per_layer = 0) {
     if (!m || !img || !logits || !boxes || !angle || !offset || !size || !depth)
         return odam_fail(1, "odam_detr_forward: null pointer");
     if (!m->finalized) return odam_fail(1, "odam_detr_forward: call odam_detr_finalize first");
@@ -388,6 +402,10 @@ int forward_impl(odam_detr* m, const float* img, int B, const unsigned char* key
     RC(lin_t(m, m->cross_v_all, m->memory_out, M, nullptr, false, m->vc, st));
 
     // ---- decoder + heads ----
+    if (frames_per_layer > 0) {      // every layer's heads inside the decoder, the last layer's included (slot L-1)
+        const LayerOut each{logits, boxes, angle, offset, size, depth, obj_features, frames_per_layer};
+        return decoder(m, B, key_mask, st, &each);
+    }
     RC(decoder(m, B, key_mask, st));
     return heads(m, B, logits, boxes, angle, offset, size, depth, obj_features, st);
 }
@@ -404,6 +422,17 @@ extern "C" int odam_detr_forward_masked(odam_detr* m, const float* img, int B, c
                                         float* size, float* depth, float* obj_features, void* stream) {
     if (!key_mask || !pos) return odam_fail(1, "odam_detr_forward_masked: null mask / position table");
     return forward_impl(m, img, B, key_mask, pos, logits, boxes, angle, offset, size, depth, obj_features, stream);
+}
+
+extern "C" int odam_detr_forward_aux(odam_detr* m, const float* img, int B, const unsigned char* key_mask, const float* pos,
+                                     float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
+                                     float* obj_features, int frames_per_layer, void* stream) {
+    if (!m || !img || !logits || !boxes || !angle || !offset || !size || !depth) return odam_fail(1, "odam_detr_forward_aux: null pointer");
+    if ((key_mask == nullptr) != (pos == nullptr))
+        return odam_fail(1, "odam_detr_forward_aux: mask and position table go together (both null for a same-size batch)");
+    if (frames_per_layer < 1 || frames_per_layer < B) return odam_fail(1, "odam_detr_forward_aux: frames_per_layer below the batch");
+    if (!m->finalized) return odam_fail(1, "odam_detr_forward_aux: call odam_detr_finalize first");
+    return forward_impl(m, img, B, key_mask, pos, logits, boxes, angle, offset, size, depth, obj_features, stream, frames_per_layer);
 }
 
 extern "C" int odam_detr_debug_read(odam_detr* m, int B, float* layer4_nchw, float* memory, void* stream) {

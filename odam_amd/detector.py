@@ -99,6 +99,19 @@ SELECT_PACK_ARGTYPES = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_fl
                         ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
 
 
+# odam_detr_forward_aux as include/odam_detr.h declares it (tests/test_detr_aux_host.py holds the two together)
+FORWARD_AUX_ARGTYPES = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_void_p] * 7 + \
+                       [ctypes.c_int, ctypes.c_void_p]
+AUX_KEYS = ("pred_logits", "pred_boxes", "pred_angle", "pred_offset", "pred_size", "pred_depth")
+
+
+def _forward_aux_entry():
+    f = _lib.lib().odam_detr_forward_aux
+    if f.argtypes is None:
+        f.argtypes, f.restype = FORWARD_AUX_ARGTYPES, ctypes.c_int
+    return f
+
+
 def _select_pack_entry():
     f = _lib.lib().odam_detr_select_pack
     if f.argtypes is None:
@@ -229,11 +242,36 @@ class Detector:
         return sine_position_embedding(h, w, self.arch["hidden_dim"] // 2, mask=mask)
 
     # ---- DETR.forward over images of different sizes (detr.py:64-65 -> misc.py:303-320) ----------------------
-    def forward_nested(self, images):
+    # ---- every decoder layer's outputs (DETR.forward with aux_loss, detr.py:89-92) ------------------------------------
+    def _layer_blocks(self, B):
+        """one [dec_layers, B, Q, .] block per output key, for odam_detr_forward_aux"""
+        a = self.arch
+        mk = lambda n: torch.empty(a["dec_layers"], B, a["num_queries"], n, device=self.device, dtype=torch.float32)
+        return {"pred_logits": mk(a["num_classes1"]), "pred_boxes": mk(4), "pred_angle": mk(a["angle_bins"]), "pred_offset": mk(2),
+                "pred_size": mk(3), "pred_depth": mk(1), "pred_obj_features": mk(a["hidden_dim"])}
+
+    def _forward_layers(self, h, x, blocks, b0, b1, mask=None, pos=None):
+        """frames b0 .. b1-1 of the blocks from the images x [b1-b0,3,H,W]: layer l of frame b lands at blocks[k][l, b]"""
+        dev = self.device
+        at = lambda k: _lib.ptr(blocks[k][0, b0:b1])          # the block's address advanced by its first frame
+        with torch.cuda.device(dev):
+            _lib.check(_forward_aux_entry()(h, _lib.ptr(x), b1 - b0, _lib.ptr(mask), _lib.ptr(pos), at("pred_logits"), at("pred_boxes"),
+                                            at("pred_angle"), at("pred_offset"), at("pred_size"), at("pred_depth"),
+                                            at("pred_obj_features"), int(blocks["pred_logits"].shape[1]),
+                                            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "odam_detr_forward_aux")
+
+    def _layer_dict(self, blocks, H, W):
+        """the output dict over the blocks: pred_* are views of the last layer's slot, aux_outputs[i] views of layer i's (no copy)"""
+        out = {k: v[-1] for k, v in blocks.items()}
+        out["aux_outputs"] = [{k: blocks[k][l] for k in AUX_KEYS} for l in range(self.arch["dec_layers"] - 1)]
+        out["_hw"] = (H, W)
+        return out
+
+    def forward_nested(self, images, aux=False):
         """list of [3,H_i,W_i] tensors -> the DETR output dict, as the reference computes it for a NestedTensor: images
         zero-padded at the top-left to the batch maximum, padding mask reduced to the token grid by nearest
         interpolation (backbone.py:79), per-image sine embedding from that mask, padded tokens excluded as attention
-        keys in the encoder and in the decoder's cross-attention."""
+        keys in the encoder and in the decoder's cross-attention.  aux=True: "aux_outputs" as well (see __call__)."""
         import torch.nn.functional as F
         imgs = [t.to(torch.float32) for t in images]
         B = len(imgs)
@@ -255,6 +293,10 @@ class Detector:
         pos = torch.stack([self._position_table(fh, fw, mask=m[i]) for i in range(B)])
         dev = self.device
         d_x, d_m, d_pos = x.to(dev), m.reshape(B, fh * fw).to(torch.uint8).to(dev).contiguous(), pos.to(dev).contiguous()
+        if aux:
+            blocks = self._layer_blocks(B)
+            self._forward_layers(h, d_x, blocks, 0, B, d_m, d_pos)
+            return self._layer_dict(blocks, H, W)
         Q = a["num_queries"]
         mk = lambda n: torch.empty(B, Q, n, device=dev, dtype=torch.float32)
         out = {"pred_logits": mk(a["num_classes1"]), "pred_boxes": mk(4), "pred_angle": mk(a["angle_bins"]),
@@ -271,15 +313,25 @@ class Detector:
         return out
 
     # ---- DETR.forward (detr.py:49-94) ---------------------------------------------------------------
-    def __call__(self, samples):
+    def __call__(self, samples, aux=False):
+        """aux=True: the same dict plus "aux_outputs", the reference's list of dec_layers - 1 dicts (the six pred_* keys of every
+        decoder layer but the last, detr.py:238-253); every value, pred_* included, is then a view into one [dec_layers, B, Q, .]
+        block per key.  Opt-in per call: build(cfg) does not read the yaml's aux_loss (a training setting), so inference never pays
+        for the five extra rounds of heads."""
         if isinstance(samples, (list, tuple)):
             if len({tuple(t.shape) for t in samples}) > 1:
-                return self.forward_nested(samples)
+                return self.forward_nested(samples, aux=aux)
             samples = torch.stack(list(samples))
         x = samples.to(self.device, torch.float32).contiguous()
         B, C, H, W = x.shape
         assert C == 3
         h = self._handle(H, W)
+        if aux:
+            blocks = self._layer_blocks(B)
+            for b0 in range(0, B, self.max_batch):
+                b1 = min(B, b0 + self.max_batch)
+                self._forward_layers(h, x[b0:b1], blocks, b0, b1)
+            return self._layer_dict(blocks, H, W)
         a = self.arch
         Q = a["num_queries"]
         dev = self.device
