@@ -36,6 +36,43 @@
  * odam_rows_gather14 -- out[i] = log[src[i]] for i < N on whole 112-byte rows, as seven 16-byte words: every bit is preserved (NaN
  * payloads, -0.0).  log and out hold N rows each, 16-byte aligned, and do not overlap; an index outside [0, N) leaves its row of
  * `out` unwritten.  N <= ODAM_ROWS_MAX_ROWS (ODAM_E_LIMIT); N == 0 returns 0 with no launch.
+ *
+ * Feeding the log from the IoU tracker (csrc/track_emit.hip, restated in numpy by tests/track_emit_ref.py).  These two
+ * replace, of the host code, odam_amd/processor.py::_track_frames_iou's copy back of the detection block and the ids, its
+ * _track_rows per frame and its grouping of one-row slices, and the upload TrackRows.load then makes of the result.
+ *
+ * odam_rows_emit_workspace -- bytes of `work` the emit call needs for N frames (0 for N == 0).
+ *
+ * odam_rows_emit_tracked -- appends the track rows of N frames' detections to the log at position base.
+ *   det_block  [dev] [N][30][15] float32, det_count [dev] [N] int32: odam_track.h's detection block and counts
+ *   ids        [dev] [N][30] int32: the tracker's out_ids          T_wc [dev] [N][4][4] float64, row-major
+ *   cam_azi    [dev] [N] float64: the camera's azimuth per frame (processor.get_cam_azi of the pose, made on the host)
+ *   N          frames; N * 30 <= ODAM_ROWS_MAX_ROWS and n_tracks <= ODAM_ROWS_MAX_TRACKS, beyond either: ODAM_E_LIMIT before
+ *              anything else is looked at.  N == 0 returns 0 with no launch (nothing is written)
+ *   rows, tid  [dev] the log, rows[cap][14] float64 (16-byte aligned) and tid[cap] int32; 0 <= base <= cap
+ *   Slot (k, d) is EMITTED iff d < min(max(det_count[k], 0), 30) and 0 <= ids[k][d] < n_tracks.  Its row goes to position
+ *   base + rank, rank = the emitted slots in front of it in (k, d) lexicographic order, and tid there becomes its id.  The row, with
+ *   r the slot's 15 float32 and T = T_wc[k], all binary64 without contraction:
+ *     columns 0, 1, 6-8   r[0], r[1], r[6..8] widened
+ *     columns 2-5         widened r[2..5] times (img_w, img_h, img_w, img_h), one multiplication each, NOT clipped
+ *     columns 9-11        ((x T[q][0] + y T[q][1]) + z T[q][2]) + T[q][3] for q = 0, 1, 2 with (x, y, z) = widened r[9..11]
+ *     column 12           atan2(widened r[12], widened r[13]) + cam_azi[k]           column 13   r[14] widened
+ *   n_emitted  [dev] [1] int32: the emitted slots (where status has ODAM_ROWS_EMIT_OVERFLOW: the slots that would have been)
+ *   counts, first_pos, last_pos   [dev] [n_tracks] int32 each: per track the rows this call wrote and the smallest and largest log
+ *              position among them (-1 where it wrote none)
+ *   status     [dev] [1] int32, a sum of ODAM_ROWS_EMIT_BAD_ID -- a live slot (d inside the clamped count) whose id is >= n_tracks:
+ *              the slot is not emitted and nothing is stored for it -- and ODAM_ROWS_EMIT_OVERFLOW -- base + n_emitted > cap: NO
+ *              row, id, count or position is stored (counts are 0, positions -1); decided from the counts before the first store
+ *   work       [dev] work_bytes >= odam_rows_emit_workspace's answer, 16-byte aligned
+ * Shape: chunks of ODAM_ROWS_CHUNK slots; a count per chunk, ONE workgroup scanning the chunk counts, a scatter that makes the
+ * flags again and ranks by ballot.  Vector stores only; integer atomics make the per-track counts and position minima / maxima
+ * only: every output has the same bits on every run.
+ *
+ * odam_rows_marks -- one small block for the host: out [n_tracks + 1][4] float64.  Row t < n_tracks: counts[t], the frame id
+ * (column 0) of the log row at first_pos[t], the frame id and the world x (column 9) of the log row at last_pos[t]; -1 for a position
+ * outside [0, n_log).  Row n_tracks: n_emitted, status, 0, 0.  With the emit call's outputs that is per track the rows added and the
+ * (first, last, last x) marks of them; a track's first row in the WHOLE log is this call's only where the track had none before, which
+ * the host knows.  n_tracks <= ODAM_ROWS_MAX_TRACKS (ODAM_E_LIMIT); one launch.
  */
 #ifndef ODAM_ROWS_H
 #define ODAM_ROWS_H
@@ -57,6 +94,18 @@ int odam_rows_group_workspace(int N, int n_tracks, size_t* bytes);
 int odam_rows_group(const int* tid, int N, int n_tracks, const int* row_off, int* src_out, int* status, void* work, size_t work_bytes,
                     void* stream);
 int odam_rows_gather14(const double* log, const int* src, int N, double* out, void* stream);
+
+#define ODAM_ROWS_EMIT_DETS 30           /* detection slots of a frame (ODAM_TRACK_DETS) */
+/* status word of odam_rows_emit_tracked: a sum of */
+#define ODAM_ROWS_EMIT_BAD_ID 1
+#define ODAM_ROWS_EMIT_OVERFLOW 2
+
+int odam_rows_emit_workspace(int N, size_t* bytes);
+int odam_rows_emit_tracked(const float* det_block, const int* det_count, const int* ids, const double* T_wc, const double* cam_azi,
+                           int N, double img_w, double img_h, int n_tracks, double* rows, int* tid, int base, int cap, int* n_emitted,
+                           int* counts, int* first_pos, int* last_pos, int* status, void* work, size_t work_bytes, void* stream);
+int odam_rows_marks(const double* rows, int n_log, const int* counts, const int* first_pos, const int* last_pos, const int* n_emitted,
+                    const int* status, int n_tracks, double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -93,7 +93,7 @@ def _associate(proc, frame_ids, T_wcs, c0, rows):
             proc.process_frame(None, int(frame_ids[c0 + i]), T_wcs[c0 + i], detections=r)
 
 
-def map_scene(proc, tracks=None, resident_rows=False, device_merge=False, stages=None):
+def map_scene(proc, tracks=None, resident_rows=False, device_merge=False, stages=None, loaded=False):
     """The back end of run_scene on ONE rank: fit -> merge -> fit over `tracks` (default: proc.tracks), returning the second
     optim_process dict (with "params" and "fitted") and filling `stages` with the seconds of fit1, merge and fit2 and the first pass's dict.
 
@@ -103,13 +103,26 @@ def map_scene(proc, tracks=None, resident_rows=False, device_merge=False, stages
               while pass 2 runs -- no concatenate and no upload of track rows after the load; the device prelude and the device merge
               are implied, and the results are theirs, bit for bit.  A list the store refuses takes the path below; a scene the device
               merge refuses (merge._device_scene) takes the host merge, followed by a load of the merged tracks.
+    loaded    with resident_rows: the store (proc._rows) holds the tracks' rows already -- a sequence fed by
+              OdamProcess.track_frames_packed(resident=True) -- so nothing is loaded: its block is taken as it stands, and the host list
+              (TrackRows.host_tracks) is downloaded under the first pass, for the result dicts and the merged host tracks.  `tracks` is
+              not used.  The store holds the MERGED tracks afterwards, so the sequence's view of it ends here: proc.tracks is the
+              unmerged host list from then on.
     device_merge   without resident_rows: proc.merge_process(out, on_device=True), as in run_scene."""
     import time
     from . import merge
-    tracks = proc.tracks if tracks is None else tracks
+    if loaded and not (resident_rows and getattr(proc, "_rows", None) is not None):
+        raise ValueError("map_scene(loaded=True) needs resident_rows=True and a row store that was fed (track_frames_packed(resident=True))")
+    release = getattr(proc, "_release_store", lambda: None)
     t = {}
     store = block = None
-    if resident_rows:
+    if loaded:
+        store = proc._rows
+        block, tracks = store.packed(), store.host_tracks
+    else:
+        tracks = proc.tracks if tracks is None else tracks
+    if resident_rows and not loaded:
+        release()      # the store is loaded below: a sequence that was a view of it keeps its list
         if proc._rows is None:
             from .track_store import TrackRows
             proc._rows = TrackRows(proc._fitter())
@@ -125,6 +138,7 @@ def map_scene(proc, tracks=None, resident_rows=False, device_merge=False, stages
         out2 = proc.optim_process_params(merged)
     else:
         out = proc.optim_process(tracks, return_params=True, rows=block)
+        release()      # (loaded: the list was downloaded under the fit; the store is about to hold other rows)
         s1 = time.perf_counter()
         proc._refine_state = None      # keyed by track index (OdamProcess.merge_process drops it too)
         packed = merge.merge_packed(out, proc.usable_frames, fitter=proc._fitter(), rows=block)

@@ -109,19 +109,26 @@ class OdamProcess:
         self.device_prelude = False  # optim_process / refine with prelude=None: True builds the fits' constraint rows on the device (multi_view.optim_process, prelude="device")
         self.resident_rows = False   # ... with prelude=None: True keeps the tracks' rows on the device between calls and uploads only the new ones (prelude="resident", track_store.TrackRows)
         self._rows = None            # the row store, made by the first call that needs it
+        self._store_auth = False     # True: the row store IS the record of the tracks (track_frames_packed(resident=True)) and `tracks` a view of it
         self.logger = logging.getLogger('OdamProcess')
 
     # `tracks` is the reference's attribute (src/processor.py:300; a list of [n, 82] arrays, index = track id).  The fast path of
     # process_frames keeps what a frame attaches as (ids, rows) records and concatenates them into the arrays only when somebody asks
     # for the list -- a concatenate per matched track per frame is a third of that path's host time otherwise.
+    # While track_frames_packed(resident=True) feeds the sequence, the rows exist on the device only (self._rows) and `tracks` is a VIEW:
+    # reading it returns self._rows.host_tracks(), one download that the store caches until it changes.  Assigning `tracks`, or a
+    # non-resident process_frames / track_frames_packed call, makes the host list the record again (_release_store).
     @property
     def tracks(self):
+        if self._store_auth:
+            return self._rows.host_tracks()
         self._sync_host_view()
         self._exposed = True
         return self._tracks
 
     @tracks.setter
     def tracks(self, value):
+        self._store_auth = False
         self._pending = []
         self._pending_app = None
         self._tracks = value
@@ -677,6 +684,7 @@ class OdamProcess:
             return None
         if trk._state is None:
             trk.reset()
+        self._release_store()      # host rows are built here: the host list is the record from now on
         if self._tracks is None or len(self._tracks) != trk.n_tracks[0]:
             raise _tracker._lib.OdamError(f"the IoU tracker holds {trk.n_tracks[0]} tracks, self.tracks "
                                           f"{None if self._tracks is None else len(self._tracks)}: init_sequence first, and do not edit the list between frames")
@@ -721,12 +729,71 @@ class OdamProcess:
             raise err
         return None
 
-    def track_frames_packed(self, blk, cnt, frame_ids, T_wcs):
+    def _release_store(self):
+        """the end of the resident mode: the list the store stands for becomes self.tracks (downloaded here unless somebody read it
+        already), and the store follows the host list through TrackRows.sync as before"""
+        if self._store_auth:
+            self.tracks = self._rows.host_tracks()
+
+    def _track_frames_resident(self, blk, cnt, frame_ids, T_wcs):
+        """_track_frames_iou with the track rows made on the device: IouTracker.step, then TrackRows.append_tracked on the ids as they
+        lie on the device.  No detection, id or row visits the host; the poses' azimuths (get_cam_azi) go up with the poses."""
+        from . import tracker as _tracker
+        trk = self._iou_tracker()
+        m = self.sequence_meta
+        n = len(frame_ids)
+        if n == 0:
+            return None
+        if trk._state is None:
+            trk.reset()
+        if self._rows is None:
+            from .track_store import TrackRows
+            self._rows = TrackRows(self._fitter())
+        if not self._store_auth:      # the store takes over from the host list: in step with it first (nothing to send in a new sequence)
+            if self._tracks is None or self._rows.sync(self.tracks) is None:
+                raise _tracker._lib.OdamError("track_frames_packed(resident=True): init_sequence first; the row store does not take this track list")
+            self._store_auth = True
+        if len(self._rows.lengths) != trk.n_tracks[0]:
+            raise _tracker._lib.OdamError(f"the IoU tracker holds {trk.n_tracks[0]} tracks, the row store {len(self._rows.lengths)}: "
+                                          "init_sequence first, and do not edit the tracks between frames")
+        T_all = np.ascontiguousarray(np.stack([np.asarray(T, np.float64) for T in T_wcs]))
+        done, err = n, None
+        try:
+            ids = trk.step(blk, cnt, np.asarray(frame_ids, np.int64), T_all, m.img_w, m.img_h)[0]
+        except _tracker.TrackOverflow as e:      # the slots from the overflow frame on are -1: emitting over all frames adds nothing for them
+            ids, done, err = e.outputs[0], e.frame, e
+        azi = np.array([get_cam_azi(T) for T in T_all])
+        self._rows.append_tracked(blk, cnt, ids, T_all, azi, m.img_w, m.img_h, trk.n_tracks[0])
+        for k in range(done):
+            self.usable_frames.append(frame_ids[k])
+            self.T_wcs.append(T_wcs[k])
+            self.P_cws.append(m.K @ np.linalg.inv(T_wcs[k])[:3, :])
+        if not self.run_associator and done:      # (four bytes back, until the first frame with a detection)
+            self.run_associator = bool((torch.as_tensor(cnt)[:done] > 0).any())
+        self._n_tracks = trk.n_tracks[0]
+        if err is not None:
+            raise err
+        return None
+
+    def track_frames_packed(self, blk, cnt, frame_ids, T_wcs, resident=False):
         """process_frames for an IouTracker on detect_frames_packed's device block (float32 [N, 30, 15] + int32 [N]): the block goes into
         the tracker's launch as it is -- the detections do not visit the host before the tracks are built; they are read back once,
-        afterwards, for the host's track rows.  Same tracks as process_frames on the unpacked rows."""
+        afterwards, for the host's track rows.  Same tracks as process_frames on the unpacked rows.
+
+        resident=True builds no host rows at all: the ids stay on the device and the track rows are written there, straight into the
+        row store (track_store.TrackRows.append_tracked); usable_frames, T_wcs, P_cws, run_associator and TrackOverflow are
+        as above.  From then on the STORE is the record of the tracks and `self.tracks` a view of it: reading it downloads the list
+        (TrackRows.host_tracks, cached until the next frames arrive; equal to the host path's list up to the rounding DESIGN 6t
+        states) and edits of that list reach nobody.  refine / optim_process with prelude="resident" and
+        pipeline.map_scene(resident_rows=True, loaded=True) take the store as it stands, without a sync and without the list.
+        The view ends, and the host list is the record again with the store following it through sync, as soon as `tracks` is
+        assigned (nothing is downloaded: the assigned list replaces the rows), a non-resident process_frames / process_frame /
+        track_frames_packed call is made, or the store is asked to stand for another list (optim_process(prelude="resident") on a
+        list that is not the view, map_scene's merge); all but the assignment download the list first."""
         if not getattr(self.associator, "iou_tracker", False):
             raise TypeError("track_frames_packed needs an odam_amd.tracker.IouTracker as the associator")
+        if resident:
+            return self._track_frames_resident(blk, cnt, frame_ids, T_wcs)
         return self._track_frames_iou(frame_ids, T_wcs, packed=(blk, cnt))
 
     # ---- back end (processor.py:347-368) -----------------------------------------------------------
@@ -757,7 +824,8 @@ class OdamProcess:
         if self.refine_fitter is None:
             self.refine_fitter = multi_view._sq.SqFitter(str(getattr(self.detector, "device", "cuda:0")), self.REFINE_MAX_ITERS)
         m = self.sequence_meta
-        tracks = self.tracks
+        # (a resident sequence fitted from its store needs the list for the result dict only: it is downloaded under the fit)
+        tracks = (lambda: self.tracks) if self._store_auth and self._prelude(prelude) == "resident" else self.tracks
         out = multi_view.optim_process(tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
                                        self.representation, prior=True, n_iters=int(n_iters), n_views=10,
                                        fitter=self.refine_fitter, return_params=return_params,
@@ -811,10 +879,16 @@ class OdamProcess:
 
     def _prelude_args(self, prelude, tracks, fitter):
         """the prelude keywords of multi_view.optim_process; "resident": the row store is brought in step with `tracks` (only rows that
-        were appended since the last call go up) and its packed block stands for them; a list the store refuses takes the device prelude"""
+        were appended since the last call go up) and its packed block stands for them; a list the store refuses takes the device prelude.
+        Where the store is the record itself (track_frames_packed(resident=True)) and `tracks` is its view -- the list self.tracks
+        returned, or a callable that will return it -- the store is taken as it stands: no sync, and the list is not needed"""
         prelude = self._prelude(prelude)
         if prelude != "resident":
             return {"prelude": prelude}
+        if self._store_auth:
+            if callable(tracks) or self._rows.is_view(tracks):
+                return {"prelude": "device", "rows": self._rows.packed()}
+            self._release_store()      # the store is to stand for another list
         if self._rows is None:
             from .track_store import TrackRows
             self._rows = TrackRows(fitter)

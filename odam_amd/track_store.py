@@ -18,18 +18,24 @@ import numpy as np
 
 from . import _lib
 
-_VP, _CI = ctypes.c_void_p, ctypes.c_int
-# the entry points as include/odam_rows.h declares them (tests/test_track_rows_host.py holds the two together)
+_VP, _CI, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+# the entry points as include/odam_rows.h declares them (tests/test_track_rows_host.py and tests/test_track_emit_host.py hold the two
+# together)
 ROWS_ARGTYPES = {
     "odam_rows_group_workspace": [_CI, _CI, _VP],
     "odam_rows_group": [_VP, _CI, _CI, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP],
     "odam_rows_gather14": [_VP, _VP, _CI, _VP, _VP],
+    "odam_rows_emit_workspace": [_CI, _VP],
+    "odam_rows_emit_tracked": [_VP, _VP, _VP, _VP, _VP, _CI, _D, _D, _CI, _VP, _VP, _CI, _CI, _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP],
+    "odam_rows_marks": [_VP, _CI, _VP, _VP, _VP, _VP, _VP, _CI, _VP, _VP],
 }
 MAX_ROWS = 1 << 24       # ODAM_ROWS_MAX_ROWS
 MAX_TRACKS = 65536       # ODAM_ROWS_MAX_TRACKS
 CHUNK = 4096             # ODAM_ROWS_CHUNK: rows one workgroup of the sort takes
 ONE_PASS_TRACKS = 256    # up to here the sort is one 8-bit pass, beyond it two
 STATUS_OK, STATUS_BAD_ID, STATUS_BAD_COUNT = 0, 1, 2
+EMIT_DETS = 30           # ODAM_ROWS_EMIT_DETS: detection slots of a frame
+EMIT_BAD_ID, EMIT_OVERFLOW = 1, 2      # odam_rows_emit_tracked's status word is a sum of these
 
 
 def _entry(name):
@@ -100,6 +106,8 @@ class TrackRows:
         self._stage_event = None              # the newest copy out of it
         self._word = None                     # pinned: the sort's status word lands here
         self.rows_uploaded = self.loads = self.groupings = 0
+        self.rows_emitted = 0                 # rows the device wrote itself (append_tracked)
+        self._host = None                     # (the packed block, the host list made from it): host_tracks' cache
         self.reset()
 
     def reset(self):
@@ -234,6 +242,95 @@ class TrackRows:
         self.capacity = max(self.n_rows, 1)
         lens_d = (off_d[1:] - off_d[:-1])
         self._tid = torch.repeat_interleave(torch.arange(T, device=rows.device, dtype=torch.int32), lens_d, output_size=self.n_rows)
+
+    # ---- rows that are born on the device (include/odam_rows.h: odam_rows_emit_tracked, odam_rows_marks) -----------------------------------
+    def _emit(self, blk, cnt, ids, T_wcs, cam_azi, img_w, img_h, n_tracks, base):
+        """the device side of append_tracked (a test's stub overrides it): both launches on the current stream, then the ONE copy back,
+        [n_tracks + 1, 4] float64 -- per track the rows added and the frame id of the first, the frame id and world x of the last of
+        them; in the last row the rows added in all and the status word"""
+        import torch
+        dev = self.device
+        as_dev = lambda x, dt, shape: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=dt))).to(
+            device=dev, dtype=getattr(torch, np.dtype(dt).name)).reshape(shape).contiguous()
+        N = int(blk.shape[0])
+        blk, cnt, ids = as_dev(blk, np.float32, (N, EMIT_DETS, 15)), as_dev(cnt, np.int32, (N,)), as_dev(ids, np.int32, (N, EMIT_DETS))
+        T, azi = as_dev(T_wcs, np.float64, (N, 4, 4)), as_dev(cam_azi, np.float64, (N,))
+        b = ctypes.c_size_t(0)
+        _lib.check(_entry("odam_rows_emit_workspace")(N, ctypes.cast(ctypes.byref(b), _VP)), "odam_rows_emit_workspace")
+        work = torch.empty(max(int(b.value), 16), device=dev, dtype=torch.uint8)
+        words = torch.empty(3 * max(n_tracks, 1) + 2, device=dev, dtype=torch.int32)      # counts, first, last; n_emitted, status
+        nt = max(n_tracks, 1)
+        counts, first, last, n_emitted, status = words[:nt], words[nt:2 * nt], words[2 * nt:3 * nt], words[3 * nt:3 * nt + 1], words[3 * nt + 1:]
+        out = torch.empty(n_tracks + 1, 4, device=dev, dtype=torch.float64)
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_entry("odam_rows_emit_tracked")(
+                _lib.ptr(blk), _lib.ptr(cnt), _lib.ptr(ids), _lib.ptr(T), _lib.ptr(azi), N, float(img_w), float(img_h), int(n_tracks),
+                _lib.ptr(self._log), _lib.ptr(self._tid), int(base), int(self.capacity), _lib.ptr(n_emitted), _lib.ptr(counts), _lib.ptr(first),
+                _lib.ptr(last), _lib.ptr(status), _lib.ptr(work), int(b.value), stream), "odam_rows_emit_tracked")
+            _lib.check(_entry("odam_rows_marks")(_lib.ptr(self._log), int(self.capacity), _lib.ptr(counts), _lib.ptr(first), _lib.ptr(last),
+                                                 _lib.ptr(n_emitted), _lib.ptr(status), int(n_tracks), _lib.ptr(out), stream), "odam_rows_marks")
+        return out.cpu().numpy()
+
+    def append_tracked(self, blk, cnt, ids, T_wcs, cam_azi, img_w, img_h, n_tracks):
+        """The track rows of N frames' detections, made ON the device from the tracker's ids and appended to the log: blk [N, 30, 15]
+        float32 + cnt [N] int32 (OdamProcess.detect_frames_packed), ids [N, 30] int32 (IouTracker.step; -1 = no row), T_wcs [N, 4, 4]
+        and cam_azi [N] float64 (processor.get_cam_azi of every pose), n_tracks = the tracks after these frames.  Device tensors are taken
+        as they are, host arrays are uploaded (the poses are host data; no track row is).  Room is reserved for the worst case, 30 N
+        rows.  One small copy back brings the rows per track and their marks; returns the rows added.  Raises OdamError -- the store
+        as it was -- where the kernel answered a status (an id >= n_tracks)."""
+        N = int(blk.shape[0])
+        n_tracks = int(n_tracks)
+        if n_tracks < len(self.lengths):
+            raise ValueError(f"append_tracked: n_tracks = {n_tracks}, the store holds {len(self.lengths)} tracks")
+        if n_tracks > MAX_TRACKS or self.n_rows + EMIT_DETS * N > MAX_ROWS:
+            raise _lib.OdamError(f"append_tracked: {n_tracks} tracks / {self.n_rows} + 30 x {N} rows are more than the store takes")
+        if N == 0:
+            return 0
+        self._reserve(self.n_rows + EMIT_DETS * N)
+        small = self._emit(blk, cnt, ids, T_wcs, cam_azi, img_w, img_h, n_tracks, self.n_rows)
+        added, status = int(small[n_tracks, 0]), int(small[n_tracks, 1])
+        if status != 0:
+            raise _lib.OdamError(f"TrackRows: odam_rows_emit_tracked answered status {status} (1: an id that is not below n_tracks = {n_tracks}, "
+                                 "2: more rows than the log holds)")
+        counts = small[:n_tracks, 0].astype(np.int64)
+        old = np.zeros(n_tracks, np.int64)
+        old[:len(self.lengths)] = self.lengths
+        marks = np.zeros((n_tracks, 3))
+        marks[:len(self.marks)] = self.marks
+        got = counts > 0
+        new = got & (old == 0)
+        marks[new, 0] = small[:n_tracks, 1][new]
+        marks[got, 1:] = small[:n_tracks, 2:4][got]
+        self.marks = marks
+        self.lengths = (old + counts).tolist()
+        self.n_rows += added
+        self.rows_emitted += added
+        if added:
+            self._grouped = False
+        self._block = self._host = None
+        return added
+
+    def is_view(self, tracks):
+        """True where `tracks` is the very list host_tracks() returned for the store as it stands"""
+        return self._host is not None and self._block is not None and self._host[0] is self._block and tracks is self._host[1]
+
+    def host_tracks(self):
+        """The host list the store stands for: [n, 82] float64 per track, as OdamProcess._track_rows(with_code=False) lays them out
+        (columns 14:78 are -1, 78:82 repeat 2:6).  Groups the store (packed()), downloads rows14 ONCE and caches the list until the
+        store changes; sync() of this list finds the store in step."""
+        block = self.packed()
+        if self._host is not None and self._host[0] is block:
+            return self._host[1]
+        rows14 = block["rows14"].cpu().numpy()
+        block["check"]()
+        full = np.full((len(rows14), 82), -1.0)
+        full[:, :14] = rows14
+        full[:, 78:82] = rows14[:, 2:6]
+        off = block["row_offsets"]
+        tracks = [full[off[t]:off[t + 1]] for t in range(block["n_tracks"])]
+        self._host = (block, tracks)
+        return tracks
 
     # ---- handing the rows out ----------------------------------------------------------------------------------------------------------------
     def packed(self):
