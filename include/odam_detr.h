@@ -156,6 +156,17 @@ int odam_detr_select_pack(const float* rows16, int B, int Q, float threshold, in
 int odam_detr_preprocess_u8(odam_detr* m, const unsigned char* rgb, int B, int h, int w, const float* mean,
                             const float* std_dev, float* out, void* stream);
 
+/* Input transform + odam_detr_forward in one call: rgb [dev][B,h,w,3] uint8 as odam_detr_preprocess_u8 takes it, the outputs as
+ * odam_detr_forward writes them.  For an fp32 model in split mode whose conv1 runs as the row convolution (odam_config stem.rows) and whose
+ * framed row pitch img_w + 8 is even, with odam_config stem.u8 = 1 (default): the resize writes the frame as centred integers in one bf16
+ * plane and conv1 reads that with the normalisation folded into its filters -- no fp32 image, no layout pass, three products per block
+ * instead of six with none dropped; the result differs from the two-call path in the last bits.  Everywhere else (bf16 / mxfp8
+ * models, cg.f32 = 0, stem.rows = 0, stem.u8 = 0, an odd pitch) the normalised image goes to a scratch of the handle's and the forward runs on
+ * it: the bits of odam_detr_preprocess_u8 + odam_detr_forward.  A caller never has to know which ran. */
+int odam_detr_forward_u8(odam_detr* m, const unsigned char* rgb, int B, int h, int w, const float* mean, const float* std_dev,
+                         float* logits, float* boxes, float* angle, float* offset, float* size, float* depth, float* obj_features,
+                         void* stream);
+
 /* Per-launch timing of the contraction kernel (all conv / linear launches of a forward are bracketed by
  * event pairs while enabled); read returns the totals of the most recent forward. */
 int odam_detr_profile_enable(odam_detr* m, int on);
@@ -245,7 +256,9 @@ int odam_op_bottleneck_f32(const float* x, const float* w2, const float* s2, con
  *   bf16.small.128x128.w8.ut
  *   bf16.ring.256x64 bf16.ring.256x128 bf16.ring.256x256 bf16.ring.512x64 bf16.ring.512x64.pool
  *   bf16.fused.p64 bf16.fused.p64.chain64 bf16.fused.p64.chain128 bf16.fused.p128 bf16.fused.p128.chain128 bf16.fused.p256
- *   BF16-TOKENS-END */
+ *   BF16-TOKENS-END
+ * conv1 on the centred uint8 frame (odam_detr_forward_u8, odam_op_stem_u8; the activations as one bf16 plane, three products per block)
+ * reports f32.ring.m5.512x64.pool, or f32.ring.m5.512x64 where the pool runs as its own kernel (tests/test_stem_u8_gpu.py covers both). */
 long long odam_op_conv_paths(char* buf, int n, int reset);
 /* which layers the bf16-native 256-row schedule of the contraction kernel takes: 0 none, 1 those large enough to fill
  * the device (default), 2 every eligible layer (parity tests on small shapes).  Process-wide; also ODAM_CG_BIG. */
@@ -259,6 +272,12 @@ int odam_op_conv_f32_mode(int mode);
 /* diagnostics: launches of conv1 with the max-pool on its tile (odam_config stem.pool) since the library was loaded -- lets a
  * test see that the fused path, not the conv1 + max-pool pair, produced what it compares */
 long long odam_op_pooled_stem_launches(void);
+/* the stem of odam_detr_forward_u8 alone: rgb [dev][B,h,w,3] uint8 -> resize to H x W -> conv1 (conv1_w [host][64,3,7,7]) -> scale / bias
+ * ([dev][64], the folded FrozenBN) -> ReLU -> 3x3 / stride 2 max-pool -> y [dev][B,H2,W2,64] fp32, through the code the forward runs.
+ * mean, std: host float[3].  *path (nullable) = 1 where conv1 read the centred bf16 frame, 0 where the normalised fp32 image was built
+ * first.  Returns 4 where conv1 would not run as the row convolution at all (cg.f32 = 0, stem.rows = 0, too few rows without cg.pin). */
+int odam_op_stem_u8(const unsigned char* rgb, int B, int h, int w, int H, int W, const float* conv1_w, const float* scale,
+                    const float* bias, const float* mean, const float* std_dev, float* y, int* path, void* stream);
 int odam_op_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                       int B, int H, int Lq, int Lk, void* stream);
 /* the same op on bf16 tensors (config 4: nn.MultiheadAttention's scaled-dot-product core, src/models/transformer.py:154-167, on

@@ -74,6 +74,9 @@ _PROTOTYPES = {
     "odam_assoc_ot_batch": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     "odam_assoc_reserve_batch": [_P, _I, _I],
     "odam_assoc_forward_batch": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    # raw uint8 frames to the detector's outputs (include/odam_detr.h), and its stem alone
+    "odam_detr_forward_u8": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "odam_op_stem_u8": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -65,6 +65,9 @@ struct ConvGemmArgs {
                                     //    association network runs on the same rows on every rank, and small tiles are what its sizes want)
     int s1_window = 0;              // set by launch_conv_gemm (bf16 ring kernel, 3x3 stride 1): one LDS window per (channel slice, ky)
                                     //    serves the three horizontal taps (odam_config.h cg.s1)
+    int a_bf16 = 0;                 // fp32 layer whose activations are exact in ONE bf16 value (the stem's centred uint8 frame): A is bf16 in memory
+                                    //    ([B, H, W] pixels of lda bf16, Cin of them per tap), never split; a x (w_hi, w_mid, w_lo) = three products per
+                                    //    block instead of six, none dropped (conv_gemm_big_kernel MODE 5: sixteen-wave 512 x 64 tiles, pre-split filters)
 };
 
 constexpr int POOL_PH = 8, POOL_PW = 14;      // pooled pixels per patch: (2 * 8 + 1) x (2 * 14 + 1) = 493 conv outputs of a 512-row tile

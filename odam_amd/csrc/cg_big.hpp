@@ -62,7 +62,7 @@ constexpr int big_lds_bytes() {
     const int ring = NST * (MODE >= 3 ? bm * 64 + 96 * BN : (bm + BN) * 64);
     const int wm = big_wm(MODE, BN, NTH);
     const int wn = NTH / 64 / wm;
-    const int slab = MODE == 4 ? (NTH / 64) * 16 * ((BN / wn > 128 ? 128 : BN / wn) + 4) * 4 : (NTH / 64) * 32 * (BN / wn) * 4;      // the 16x16x32 loop's epilogue: 16-row slabs, rows padded by 4
+    const int slab = MODE >= 4 ? (NTH / 64) * 16 * ((BN / wn > 128 ? 128 : BN / wn) + 4) * 4 : (NTH / 64) * 32 * (BN / wn) * 4;      // the 16x16x32 loop's epilogue: 16-row slabs, rows padded by 4
     const int s1 = (MODE == 0 && NTH == 512) ? (BN == 256 ? 2 : (BN == 128 ? 3 : 4)) * (384 * 64 + 3 * BN * 64) : 0;   // the 3x3 stride-1 window ring (bf16)
     const int m = ring > slab ? ring : slab;
     const int deep = big_deep_a(MODE, BN, NST, NTH) ? (6 + 4) * 256 * 64 : 0;      // six activation + four filter slots (see the main loop)
@@ -76,16 +76,23 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
                       (FUSE >= 5 && FUSE <= 8 && MODE == 0 && NTH == 512 && NST == 4),
                   "fused layers: pre-split filters with 64-column tiles (FUSE 1, 2, 4) or 128-column tiles (FUSE 3); bf16 (FUSE 5 + "
                   "log2(PN / 32), 5 = no chained reduce)");
-    static_assert(MODE == 0 || MODE == 2 || MODE == 3 || MODE == 4,
-                  "bf16 operands, fp32 split, fp32 split with pre-split filters (3: 32x32x16 matrix instruction, 4: 16x16x32)");
+    static_assert(MODE == 0 || MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5,
+                  "bf16 operands, fp32 split, fp32 split with pre-split filters (3: 32x32x16 matrix instruction, 4: 16x16x32, 5: 16x16x32 "
+                  "with the activations as ONE bf16 plane in memory)");
     static_assert(MODE != 4 || FUSE <= 4, "the 16x16x32 schedule: its own epilogue, or the fp32 bottleneck tails");
     constexpr bool BF16 = MODE == 0;
     // MODE 3 = MODE 2 with the FILTERS split ahead of time (a.Wt3: [Cout][Kpad / 16][3][16] bf16 = hi | mid | lo of every
     // 16-k group): they arrive in LDS as three bf16 planes and go to the matrix pipe as they are, only the activations are
     // split in registers; the wave grid is 4 x 2 (64 x 128 per wave), so a wave splits 2 row tiles instead of 4 + 2
     // -- a third of the vector work of MODE 2.
-    constexpr bool PRE = MODE == 3 || MODE == 4;
-    constexpr bool X16 = MODE == 4;          // pre-split filters, v_mfma_f32_16x16x32_bf16: see the main loop
+    constexpr bool PRE = MODE == 3 || MODE == 4 || MODE == 5;
+    constexpr bool X16 = MODE == 4 || MODE == 5;      // pre-split filters, v_mfma_f32_16x16x32_bf16: see the main loop
+    // MODE 5 = MODE 4 for activations that are exact in ONE bf16 value (ConvGemmArgs::a_bf16: the stem's centred uint8 frame): they lie in
+    // memory as bf16, one 64-byte row per 32 k, go to the matrix pipe as they arrive, and a block is the three products a x (hi, mid, lo)
+    constexpr bool A16 = MODE == 5;
+    static_assert(!A16 || (NTH == 1024 && BN == 64 && FUSE == 0), "bf16 activations: the sixteen-wave 512 x 64 tile only");
+    constexpr int AES = A16 ? 2 : (int)sizeof(typename std::conditional<BF16, unsigned short, float>::type);      // bytes per activation element in memory
+    constexpr int AEPC = 16 / AES;
     static_assert(!PRE || NTH == 512 || (X16 && NTH == 1024), "pre-split filters: eight-wave workgroups, or sixteen waves (16x16x32 loop)");
     static_assert(NTH != 1024 || (FUSE == 0 && ((BN == 64 && (X16 || BF16)) || (BN == 256 && BF16))), "sixteen waves: plain layers (512 x 64: bf16 or the 16x16x32 split loop; 256 x 256: bf16)");
     using T = typename std::conditional<BF16, unsigned short, float>::type;
@@ -122,7 +129,7 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
     const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     // stem with the max-pool on the tile (ConvGemmArgs::pool): tile = a 2-D patch of conv outputs, (b, first row, first column)
-    constexpr bool POOLABLE = NTH == 1024 && BN == 64 && FUSE == 0 && (MODE == 4 || MODE == 0);
+    constexpr bool POOLABLE = NTH == 1024 && BN == 64 && FUSE == 0 && (X16 || MODE == 0);
     constexpr int pl_tw = 2 * POOL_PW + 1, pl_rows = (2 * POOL_PH + 1) * pl_tw;      // patch: 17 x 29 conv outputs
     static_assert(pl_rows <= 512, "a patch fits a 512-row tile");
     int pl_b = 0, pl_y0 = 0, pl_x0 = 0;
@@ -178,9 +185,10 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
     const int kw_inv = (65536 + a.KW - 1) / a.KW;
     const int nt_inv = (65536 + ntaps - 1) / ntaps;
     const int b0 = (POOLABLE && a.pool) ? pl_b : m0 / hw;
-    const int csrc = X16 ? (c4 ^ ((lane >> 4) & 1)) : (c4 ^ ((lane >> 4) & 3));     // 16-row fragments: rows r, r + 4 differ in the key (see X16)
+    const int csrc = A16 ? (c4 ^ ((0 - (lane >> 4)) & 3))       // one chunk per lane and 32 k: key (-(r >> 2)) & 3 (see A16 in the main loop)
+                   : X16 ? (c4 ^ ((lane >> 4) & 1)) : (c4 ^ ((lane >> 4) & 3));     // 16-row fragments: rows r, r + 4 differ in the key (see X16)
     const int margin = (a.pad * a.W + a.pad) * lda;
-    const unsigned long long pa = (unsigned long long)(Ag + (size_t)b0 * a.H * a.W * lda - margin), pw = (unsigned long long)Wg;
+    const unsigned long long pa = (unsigned long long)a.A + ((size_t)b0 * a.H * a.W * lda - (size_t)margin) * AES, pw = (unsigned long long)Wg;
     const u32x4 a_rs4 = u32x4{(unsigned)pa, (unsigned)(pa >> 32) & 0xffffu, OOB_VOFF, 0x00020000u};
     const u32x4 w_rs4 = u32x4{(unsigned)pw, (unsigned)(pw >> 32) & 0xffffu, OOB_VOFF, 0x00020000u};
     unsigned a_voff[A_LD], a_mask[A_LD], w_voff[B_LD];
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
             iy0 = oy * a.stride - a.pad; ix0 = ox * a.stride - a.pad;
             base = ((b * a.H + iy0) * a.W + ix0) * lda;
         }
-        a_voff[i] = (unsigned)(base - b0 * a.H * a.W * lda + margin + csrc * EPC) * (unsigned)sizeof(T);
+        a_voff[i] = (unsigned)(base - b0 * a.H * a.W * lda + margin + csrc * AEPC) * (unsigned)AES;
         unsigned mk = plain ? 1u : 0u;
         for (int t = 0; t < (plain ? 0 : ntaps); t++) {
             const int ky = (t * kw_inv) >> 16, kx = t - ky * a.KW;
@@ -422,8 +430,9 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
             const TilePrep tp = tile_prep(kt);
 #pragma unroll
             for (int part = 0; part < A_LD; part++) {
+                if (A16 && (kt & 1)) break;      // bf16 activations: the even stage's row holds the pair's 32 k
                 const unsigned vo = ((a_mask[part] >> tp.tap) & 1u) ? a_voff[part] : OOB_VOFF;
-                lds_dma16(a_rs4, lds_base + (unsigned)(st * STAGE + wave_u * 16 * ROWB + RPP * part * ROWB), vo, tp.soff_a);
+                lds_dma16(a_rs4, lds_base + (unsigned)(st * STAGE + wave_u * 16 * ROWB + RPP * part * ROWB), vo, A16 ? tp.soff_a >> 1 : tp.soff_a);
             }
 #pragma unroll
             for (int j = 0; j < B3_HI; j++)
@@ -445,7 +454,7 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
             const TilePrep tp = tile_prep(kt);
             if (part < A_LD) {
                 const unsigned vo = ((a_mask[part] >> tp.tap) & 1u) ? a_voff[part] : OOB_VOFF;
-                lds_dma16(a_rs4, lds_base + (unsigned)(st * STAGE + wave_u * 16 * ROWB + RPP * part * ROWB), vo, tp.soff_a);
+                lds_dma16(a_rs4, lds_base + (unsigned)(st * STAGE + wave_u * 16 * ROWB + RPP * part * ROWB), vo, A16 ? tp.soff_a >> 1 : tp.soff_a);
             } else {
                 const int j = part - A_LD;
                 if (j + 1 < B3_HI || b_wave)
@@ -469,6 +478,50 @@ __global__ __launch_bounds__(NTH, (NTH == 1024 ? 4 : 2)) void conv_gemm_big_kern
         unsigned long long st_acc[4] = {0, 0, 0, 0}, st_prev = __builtin_readcyclecounter();
         const unsigned long long st_loop0 = st_prev;
 #endif
+        if constexpr (A16) {
+            // ---- bf16 activations (MODE 5) ---------------------------------------------------------------------------------------
+            // A pair's activations are ONE 64-byte row per tile row (32 bf16 k) in the pair's even stage; the filter planes lie in both
+            // stages exactly as above.  Lane (row l & 15, k-group kq = l >> 4) reads the 16-byte chunk kq of its row at kq ^ key,
+            // key = (-(row >> 2)) & 3: the read groups of ds_read_b128 see rows 0-3 / 12-15 with chunk c and rows 4-11 with chunk
+            // c ^ 1, and this key puts the four rows that share a bank range on four different chunks (reasoned from those groups as
+            // the keys above are; not measured with counters).  No split, no second
+            // register set: per pair a wave reads MI + 3 NJ fragments, issues A_LD + 2 B3_HI DMAs and 3 MI NJ matrix
+            // instructions, hi, mid, lo on every accumulator.  The ring bookkeeping is the loop's below: a DMA past the last
+            // k-block is not issued (dma_part16), so nothing is in flight when the epilogue takes the ring.
+            const int a5_lane = (wm * (BM / WM) + r16) * ROWB + ((kq ^ ((0 - (r16 >> 2)) & 3)) << 4);
+            constexpr int NA5 = A_LD, NDMA5 = NA5 + 2 * B3_HI, NBLK5 = MI * NJ;
+            for (int kp = 0; 2 * kp < nk; ++kp) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this pair has landed (the next one is issued below)
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                const int s0 = (2 * kp) & 3;
+                const char* Sa = lds_c + s0 * STAGE + a5_lane;
+                const char* Sb = lds_c + s0 * STAGE + b_lane;
+                uint4 av[MI], bh[NJ], bm[NJ], bl[NJ];
+#pragma unroll
+                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const uint4*>(Sa + mi * 16 * ROWB);
+#pragma unroll
+                for (int j = 0; j < NJ; j++) {
+                    const char* bp = Sb + j * 16 * 32;
+                    bh[j] = *reinterpret_cast<const uint4*>(bp);
+                    bm[j] = *reinterpret_cast<const uint4*>(bp + BN * 32);
+                    bl[j] = *reinterpret_cast<const uint4*>(bp + 2 * BN * 32);
+                }
+                int dpart = 0;
+#pragma unroll
+                for (int b = 0; b < NBLK5; b++) {
+                    const int mi = b / NJ, nj = b % NJ;
+                    ODAM_MM16(c16[mi][nj], av[mi], bh[nj]); ODAM_MM16(c16[mi][nj], av[mi], bm[nj]); ODAM_MM16(c16[mi][nj], av[mi], bl[nj]);
+#pragma unroll
+                    for (; dpart < ((b + 1) * NDMA5 + NBLK5 - 1) / NBLK5; dpart++) {
+                        const int half_ = dpart < NA5 ? 0 : (dpart - NA5) / B3_HI;
+                        const int part = dpart < NA5 ? dpart : A_LD + (dpart - NA5) % B3_HI;
+                        dma_part16(2 * kp + 2 + half_, (s0 ^ 2) + half_, part);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        } else
         for (int kp = 0; 2 * kp < nk; ++kp) {
             CG_STAMP_AT(3);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this pair has landed (the next one is issued below)
@@ -1200,7 +1253,7 @@ static int launch_big(const ConvGemmArgs& a_in, int s1_window, hipStream_t strea
     constexpr int bm = big_bm(BN, NTH);
     int tiles = ((a.M + bm - 1) / bm) * ((a.Cout + BN - 1) / BN);
     if (a.pool) {
-        if (!(NTH == 1024 && BN == 64 && (MODE == 4 || MODE == 0)) || a.Cout != 64 || a.pool_ph != POOL_PH || a.pool_pw != POOL_PW ||
+        if (!(NTH == 1024 && BN == 64 && (MODE == 4 || MODE == 5 || MODE == 0)) || a.Cout != 64 || a.pool_ph != POOL_PH || a.pool_pw != POOL_PW ||
             a.ldc != a.Cout || a.res)
             return odam_fail(1, "conv_gemm: pooled stem asked for where it does not apply");
         tiles = a.B * ((a.Hp + POOL_PH - 1) / POOL_PH) * ((a.Wp + POOL_PW - 1) / POOL_PW);

@@ -21,7 +21,8 @@ struct Choice {
     int bm = 0, bn = 0, waves = 0;        // tile rows x columns and wavefronts per workgroup (fused: bn = the 3x3's channels, 256 rows, 8 waves)
     int stages = 2;                       // Small: LDS stages (4 = the deep LDS-DMA pipeline)
     bool ut = false, x3 = false;          // Small: uniform-tap LDS-DMA gather; fp32 products through the exact bf16 split
-    int mode = 0;                         // RingF32 / FusedF32: 2 split in registers, 3 pre-split filters on 32x32x16, 4 pre-split on 16x16x32
+    int mode = 0;                         // RingF32 / FusedF32: 2 split in registers, 3 pre-split filters on 32x32x16, 4 pre-split on 16x16x32,
+                                          // 5 = 4 with the activations as one bf16 plane in memory (ConvGemmArgs::a_bf16)
     bool pool = false;                    // ring kernels: the stem's max-pool on the tile
     int chain = 0;                        // fused: output channels of the next block's reduce riding along (0: none)
     int s1_window = 0;                    // ConvGemmArgs::s1_window of the launch
@@ -40,6 +41,8 @@ void choice_token(const Choice& c, char* tok);
 bool fused_second_ok(const ConvGemmArgs& a, const Switches& sw);      // fp32 split mode: 3x3 + expand (+ next reduce) as one launch (cg.fuse)
 bool fused_bf16_ok(const ConvGemmArgs& a, const Switches& sw);        // bf16: the same with F_Wt [+ G_Wt] (cg.fuse_bf16)
 bool pooled_stem_ok(const ConvGemmArgs& a, const Switches& sw);       // the stem with the max-pool on the tile (stem.pool)
+bool bf16_plane_ok(const ConvGemmArgs& a, const Switches& sw);        // fp32 layer on activations stored as one bf16 plane (a_bf16; with pool: and pooled)
+bool bf16_plane_ok(const ConvGemmArgs& a);
 bool fused_second_ok(const ConvGemmArgs& a);
 bool fused_bf16_ok(const ConvGemmArgs& a);
 bool pooled_stem_ok(const ConvGemmArgs& a);

@@ -153,7 +153,20 @@ bool pooled_stem_ok(const ConvGemmArgs& a, const Switches& sw) {
     return ring_eligible(a, sw, 64) && fills_512_row_tiles(a, sw);
 }
 
+// activations as one bf16 plane (a_bf16): the sixteen-wave 512 x 64 tile of the 16x16x32 split loop, nothing else -- pre-split filters, 32 k
+// (one 64-byte row) inside one tap, every row's first pixel on a 16-byte boundary (pixel pitch x stride, row pitch and image size in
+// bytes), a device-filling problem; with `pool` set, whatever the pooled stem asks as well
+bool bf16_plane_ok(const ConvGemmArgs& a, const Switches& sw) {
+    if (is_bf16(a) || !sw.ring || !(sw.tiles & 8) || ring_mode_f32(a, sw) != 4) return false;
+    if (a.Cout <= 32 || a.Cout > 64 || a.Cin % 32 != 0 || a.res) return false;
+    const long lda = a.lda > 0 ? a.lda : a.Cin;
+    if ((lda * a.stride * 2) % 16 != 0 || (lda * a.W * 2) % 16 != 0 || (lda * a.pad * 2) % 16 != 0) return false;
+    if (a.pool && !pooled_stem_ok(a, sw)) return false;
+    return ring_eligible(a, sw, 64) && fills_512_row_tiles(a, sw);
+}
+
 bool fused_second_ok(const ConvGemmArgs& a) { return fused_second_ok(a, current_switches()); }
+bool bf16_plane_ok(const ConvGemmArgs& a) { return bf16_plane_ok(a, current_switches()); }
 bool fused_bf16_ok(const ConvGemmArgs& a) { return fused_bf16_ok(a, current_switches()); }
 bool pooled_stem_ok(const ConvGemmArgs& a) { return pooled_stem_ok(a, current_switches()); }
 bool presplit_applies(int Cout, int Kpad) { return f32_mode() == 2 && split_planes_fit(Cout, Kpad); }
@@ -168,6 +181,10 @@ Choice choose(const ConvGemmArgs& a, const Switches& sw) {
     if (a.M <= 0 || a.Cout <= 0) return Choice{};
 
     // ---- what the caller asked for by name: it runs so, or the call is refused -----------------------------------------------
+    if (a.a_bf16) {
+        if (!bf16_plane_ok(a, sw)) return refuse("conv_gemm: bf16-plane activations asked for where they do not apply (check bf16_plane_ok)");
+        return ring(a, sw, 5, 64, 16);
+    }
     if (a.pool) {
         if (!pooled_stem_ok(a, sw)) return refuse("conv_gemm: pooled stem asked for where it does not apply (check pooled_stem_ok)");
         return ring(a, sw, bf ? 0 : 4, 64, 16);

@@ -6,7 +6,8 @@
 namespace odam_cg {
 
 // plain layers, fp32 operands: mode 2 (split in registers), 3 (pre-split filters, 32x32x16), 4 (pre-split, 16x16x32);
-// bn = tile columns 64 / 128 / 256; nth = 512, or 1024 for the sixteen-wave 512 x 64 tiles of mode 4
+// bn = tile columns 64 / 128 / 256; nth = 512, or 1024 for the sixteen-wave 512 x 64 tiles of mode 4 and of mode 5 (mode 4 on activations
+// stored as one bf16 plane, ConvGemmArgs::a_bf16)
 int launch_big_f32(int mode, int bn, int nth, const ConvGemmArgs& a, hipStream_t stream);
 // plain layers, bf16 operands: bn 64 / 128 / 256, nth 512 or 1024 (bn 64 and 256)
 int launch_big_bf16(int bn, int nth, int s1_window, const ConvGemmArgs& a, hipStream_t stream);

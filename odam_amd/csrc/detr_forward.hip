@@ -120,6 +120,17 @@ int stem_rows_t(odam_detr* m, int B, hipStream_t st, void* pooled_out, bool* poo
                             [&] { return odam_cg::launch_conv_gemm(a, st); });
 }
 
+// conv1 on the centred uint8 frame in m->x4 (four bf16 per pixel, preprocess_u8_bf16x4_framed_kernel) with the folded filters w3: the
+// row-convolution stem's geometry, the activations as one bf16 plane (ConvGemmArgs::a_bf16); pool: the max-pool on the tile, into bufA
+ConvGemmArgs stem_u8_args(odam_detr* m, int B, const void* w3, bool pool) {
+    ConvGemmArgs a = conv_args(m->stem_rows, m->x4, B, m->cfg.img_h + 6, m->cfg.img_w + 8, 0);
+    a.Wt3 = w3; a.a_bf16 = 1;
+    a.lda = 4; a.Ho = m->H1; a.Wo = m->W1; a.M = B * a.Ho * a.Wo;
+    a.relu = 1; a.C = m->stem_out;
+    if (pool) { a.pool = 1; a.pool_ph = odam_cg::POOL_PH; a.pool_pw = odam_cg::POOL_PW; a.Hp = m->H2; a.Wp = m->W2; a.C = m->bufA; }
+    return a;
+}
+
 // an mxfp8 body layer: x / xs MXFP8 input, res bf16 (nullable); outputs y / ys MXFP8 and / or yb bf16 (nullable)
 int mx_t(odam_detr* m, const Conv& c, const unsigned char* x, const unsigned char* xs, int B, int H, int W, const void* res, bool relu,
          unsigned char* y, unsigned char* ys, void* yb, hipStream_t st) {
@@ -157,12 +168,8 @@ int stem(odam_detr* m, const float* img, int B, hipStream_t st) {
     // convolution with "Cin" = 32 floats per row, pixel stride lda = 4, no padding, K = 224 instead of 147 + pad --
     // a third of the products are zeros, on a path that is 2-3x faster than the 128x64 tiles of the fp32 instruction.
     const int dt = m->dt, ih = m->cfg.img_h, iw = m->cfg.img_w;
-    const bool rows_ok = odam_cfg::get(odam_cfg::STEM_ROWS) != 0;
     bool pooled = false;
-    const long Mst = (long)B * m->H1 * m->W1;
-    const bool rows_mode = dt ? (m->stem_rows.w != nullptr && odam_cfg::get(odam_cfg::CG_RING) != 0)
-                              : (m->stem_rows.w3 != nullptr && odam_cg::f32_mode() == 2);
-    if (rows_ok && rows_mode && (Mst >= 192L * 256 || odam_cfg::get(odam_cfg::CG_PIN))) {
+    if (stem_rows_applies(m, B)) {
         RC(odam_dk::launch_nchw_to_nhwc4_framed(img, m->x4, B, ih, iw, dt, st));
         RC(stem_rows_t(m, B, st, m->bufA, &pooled));
     } else {
@@ -172,6 +179,53 @@ int stem(odam_detr* m, const float* img, int B, hipStream_t st) {
     if (!pooled) RC(odam_dk::launch_maxpool3x3s2(m->stem_out, m->bufA, B, m->H1, m->W1, 64, m->H2, m->W2, dt, st));
     return 0;
 }
+
+}  // namespace
+
+namespace odam_dm {
+
+bool stem_rows_applies(const odam_detr* m, int B) {
+    const long Mst = (long)B * m->H1 * m->W1;
+    const bool rows_mode = m->dt ? (m->stem_rows.w != nullptr && odam_cfg::get(odam_cfg::CG_RING) != 0)
+                                 : (m->stem_rows.w3 != nullptr && odam_cg::f32_mode() == 2);
+    return odam_cfg::get(odam_cfg::STEM_ROWS) != 0 && rows_mode && (Mst >= 192L * 256 || odam_cfg::get(odam_cfg::CG_PIN));
+}
+
+// The stem from raw frames.  Where the model is fp32 in split mode, conv1 runs as the row convolution, the framed row pitch is even
+// (every stride-2 output's first pixel on a 16-byte boundary) and stem.u8 is on: ONE producer pass writes the centred integers as the
+// framed bf16 image (8 bytes per pixel) and conv1 reads that with three products per block (conv_gemm_big_kernel MODE 5).  Otherwise
+// the normalised fp32 image goes to a scratch of the model's and the stem runs as odam_detr_forward runs it: the same bits as
+// odam_detr_preprocess_u8 + odam_detr_forward.
+int stem_from_u8(odam_detr* m, const unsigned char* rgb, int B, int h, int w, const float* mean, const float* stdv, hipStream_t st, int* path) {
+    const int ih = m->cfg.img_h, iw = m->cfg.img_w;
+    odam_detr::Resample tx{}, ty{};
+    RC(resample_tables(m, h, w, &tx, &ty));
+    if (path) *path = 0;
+    if (odam_cfg::get(odam_cfg::STEM_U8) != 0 && m->dt == 0 && !m->mx && (iw + 8) % 2 == 0 && !m->conv1_w.empty() && stem_rows_applies(m, B)) {
+        // (a cheap test first -- the filters are built only where the kernel would take them)
+        bool pooled = odam_cg::bf16_plane_ok(stem_u8_args(m, B, m->stem_rows.w3, true));
+        if (pooled || odam_cg::bf16_plane_ok(stem_u8_args(m, B, m->stem_rows.w3, false))) {
+            const odam_detr::StemU8* f = nullptr;
+            RC(stem_u8_filters(m, mean, stdv, &f));
+            RC(odam_dk::launch_preprocess_u8_bf16x4_framed(rgb, B, h, w, tx.xmin, tx.cnt, tx.K, tx.ksize, ty.xmin, ty.cnt, ty.K, ty.ksize,
+                                                           m->x4, ih, iw, f->centre, st));
+            const ConvGemmArgs a = stem_u8_args(m, B, f->w3, pooled);
+            if (pooled) g_pooled_stem_launches.fetch_add(1);
+            RC(m->conv_ev.timed(st, 2.0 * a.M * (double)a.Cout * 147, [&] { return odam_cg::launch_conv_gemm(a, st); }));
+            if (!pooled) RC(odam_dk::launch_maxpool3x3s2(m->stem_out, m->bufA, B, m->H1, m->W1, 64, m->H2, m->W2, 0, st));
+            if (path) *path = 1;
+            return 0;
+        }
+    }
+    if (!m->u8_img) RC(m->dev_alloc(&m->u8_img, (size_t)m->cfg.max_batch * 3 * ih * iw));
+    RC(odam_dk::launch_preprocess_u8(rgb, B, h, w, tx.xmin, tx.cnt, tx.K, tx.ksize, ty.xmin, ty.cnt, ty.K, ty.ksize, m->u8_img, ih, iw, mean,
+                                     stdv, st));
+    return stem(m, m->u8_img, B, st);
+}
+
+}  // namespace odam_dm
+
+namespace {
 
 // mxfp8: every body convolution on MXFP8 operands, one launch per layer (cg_mx8.hip).  Block inputs / outputs are
 // written in both forms -- MXFP8 (cq / cs, read by conv1 and the downsample) and bf16 (cur, read as the residual); the
@@ -369,13 +423,15 @@ int decoder(odam_detr* m, int B, const unsigned char* key_mask, hipStream_t st, 
     return 0;
 }
 
+struct RawFrames { const unsigned char* rgb; int h, w; const float *mean, *stdv; };      // odam_detr_forward_u8: the stem reads these, not img
+
 // key_mask / pos_b: null for same-size batches (no padding: the mask is all false and one position table serves every
 // image).  Otherwise key_mask [B][L] marks padded tokens (backbone.py:79) and pos_b [B][L][E] is each image's own sine
 // embedding, which depends on its mask (position_encoding.py:26-46).
 int forward_impl(odam_detr* m, const float* img, int B, const unsigned char* key_mask, const float* pos_b,
                  float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
-                 float* obj_features, void* stream, int frames_per_layer = 0) {
-    if (!m || !img || !logits || !boxes || !angle || !offset || !size || !depth)
+                 float* obj_features, void* stream, int frames_per_layer = 0, const RawFrames* raw = nullptr) {
+    if (!m || (!img && !raw) || !logits || !boxes || !angle || !offset || !size || !depth)
         return odam_fail(1, "odam_detr_forward: null pointer");
     if (!m->finalized) return odam_fail(1, "odam_detr_forward: call odam_detr_finalize first");
     if (B < 1 || B > m->cfg.max_batch) return odam_fail(3, "odam_detr_forward: batch outside 1..max_batch");
@@ -383,7 +439,8 @@ int forward_impl(odam_detr* m, const float* img, int B, const unsigned char* key
     m->conv_ev.used = m->att_ev.used = 0;
 
     // ---- backbone (backbone.py:59-94) ----
-    RC(stem(m, img, B, st));
+    if (raw) RC(stem_from_u8(m, raw->rgb, B, raw->h, raw->w, raw->mean, raw->stdv, st, nullptr));
+    else RC(stem(m, img, B, st));
     std::fill(m->stage_ev, m->stage_ev + 6, m->conv_ev.used);
     m->stage_ev[0] = 0;
     Act s{m->bufA, m->bufB, m->H2, m->W2};
@@ -415,6 +472,15 @@ int forward_impl(odam_detr* m, const float* img, int B, const unsigned char* key
 extern "C" int odam_detr_forward(odam_detr* m, const float* img, int B, float* logits, float* boxes, float* angle,
                                  float* offset, float* size, float* depth, float* obj_features, void* stream) {
     return forward_impl(m, img, B, nullptr, nullptr, logits, boxes, angle, offset, size, depth, obj_features, stream);
+}
+
+extern "C" int odam_detr_forward_u8(odam_detr* m, const unsigned char* rgb, int B, int h, int w, const float* mean, const float* stdv,
+                                    float* logits, float* boxes, float* angle, float* offset, float* size, float* depth,
+                                    float* obj_features, void* stream) {
+    if (!rgb || !mean || !stdv) return odam_fail(1, "odam_detr_forward_u8: null pointer");
+    if (h < 1 || w < 1) return odam_fail(1, "odam_detr_forward_u8: bad size");
+    const RawFrames raw{rgb, h, w, mean, stdv};
+    return forward_impl(m, nullptr, B, nullptr, nullptr, logits, boxes, angle, offset, size, depth, obj_features, stream, 0, &raw);
 }
 
 extern "C" int odam_detr_forward_masked(odam_detr* m, const float* img, int B, const unsigned char* key_mask,

@@ -57,6 +57,11 @@ static int resample_table(odam_detr* m, int in_size, int out_size, odam_detr::Re
     return 0;
 }
 
+int odam_dm::resample_tables(odam_detr* m, int h, int w, odam_detr::Resample* tx, odam_detr::Resample* ty) {
+    RC(resample_table(m, w, m->cfg.img_w, tx));
+    return resample_table(m, h, m->cfg.img_h, ty);
+}
+
 // transforms.py:281-290 on the device: resize to the model's (img_h, img_w) + ToTensor + Normalize
 extern "C" int odam_detr_preprocess_u8(odam_detr* m, const unsigned char* rgb, int B, int h, int w, const float* mean,
                                        const float* stdv, float* out, void* stream) {

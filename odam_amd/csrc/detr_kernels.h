@@ -52,6 +52,10 @@ int launch_postprocess(const float* logits, const float* boxes, const float* ang
 
 // Input transform on the device: uint8 [B,h,w,3] -> float32 [B,3,H,W] = Normalize(ToTensor(PIL-bilinear resize)),
 // bit-identical to the host transform (resampling tables: detr_input.hip resample_table, 22-bit fixed point)
+// the same resize written as the framed NHWC4 image of four bf16 per pixel (u - centre, 1) that the uint8 stem reads: out [B][H + 6][W + 8][4]
+int launch_preprocess_u8_bf16x4_framed(const unsigned char* rgb, int B, int h, int w, const int* tx_xmin, const int* tx_cnt,
+                                       const int* tx_K, int tx_ksize, const int* ty_xmin, const int* ty_cnt, const int* ty_K,
+                                       int ty_ksize, void* out, int H, int W, const int centre[3], hipStream_t stream);
 int launch_preprocess_u8(const unsigned char* rgb, int B, int h, int w, const int* tx_xmin, const int* tx_cnt,
                          const int* tx_K, int tx_ksize, const int* ty_xmin, const int* ty_cnt, const int* ty_K,
                          int ty_ksize, float* out, int H, int W, const float mean[3], const float stdv[3],

@@ -5,6 +5,7 @@
 
 #include "odam_config.h"
 #include "odam_err.h"
+#include "stem_u8_fold.h"
 
 namespace odam_dk {
 
@@ -1045,15 +1046,9 @@ __device__ __forceinline__ int clip8_22(int v) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-__global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char* __restrict__ rgb, int h, int w,
-                                                            ResampleTable tx, ResampleTable ty, int need_x, int need_y,
-                                                            float* __restrict__ out, int H, int W, float3 mean,
-                                                            float3 stdv) {
-    const int X = blockIdx.x * 256 + threadIdx.x;
-    const int Y = blockIdx.y;
-    const size_t b = blockIdx.z;
-    if (X >= W) return;
-    const unsigned char* img = rgb + b * (size_t)h * w * 3;
+// the resized frame's three bytes at output pixel (X, Y) of image `img` [h][w][3]: both integer passes, as Pillow rounds them
+__device__ __forceinline__ void resample_u8_pixel(const unsigned char* __restrict__ img, int w, const ResampleTable& tx, const ResampleTable& ty,
+                                                  int need_x, int need_y, int X, int Y, int& u0, int& u1, int& u2) {
     const int x0 = need_x ? tx.xmin[X] : X, nx = need_x ? tx.cnt[X] : 1;
     const int y0 = need_y ? ty.xmin[Y] : Y, ny = need_y ? ty.cnt[Y] : 1;
     const int* kx = tx.K + (size_t)X * tx.ksize;
@@ -1079,9 +1074,21 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char*
         }
         last[0] = hv[0]; last[1] = hv[1]; last[2] = hv[2];
     }
-    const int u0 = need_y ? clip8_22(acc[0]) : last[0];
-    const int u1 = need_y ? clip8_22(acc[1]) : last[1];
-    const int u2 = need_y ? clip8_22(acc[2]) : last[2];
+    u0 = need_y ? clip8_22(acc[0]) : last[0];
+    u1 = need_y ? clip8_22(acc[1]) : last[1];
+    u2 = need_y ? clip8_22(acc[2]) : last[2];
+}
+
+__global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char* __restrict__ rgb, int h, int w,
+                                                            ResampleTable tx, ResampleTable ty, int need_x, int need_y,
+                                                            float* __restrict__ out, int H, int W, float3 mean,
+                                                            float3 stdv) {
+    const int X = blockIdx.x * 256 + threadIdx.x;
+    const int Y = blockIdx.y;
+    const size_t b = blockIdx.z;
+    if (X >= W) return;
+    int u0, u1, u2;
+    resample_u8_pixel(rgb + b * (size_t)h * w * 3, w, tx, ty, need_x, need_y, X, Y, u0, u1, u2);
     // ToTensor: float32(u8) / 255; Normalize: (x - mean) / std, float32 (transforms.py:222-243)
     const size_t plane = (size_t)H * W, o = (b * 3 * H + Y) * (size_t)W + X;
     out[o] = ((float)u0 / 255.0f - mean.x) / stdv.x;
@@ -1098,6 +1105,39 @@ int launch_preprocess_u8(const unsigned char* rgb, int B, int h, int w, const in
     hipLaunchKernelGGL(preprocess_u8_kernel, dim3((W + 255) / 256, H, B), dim3(256), 0, stream, rgb, h, w, tx, ty,
                        (int)(W != w), (int)(H != h), out, H, W, float3{mean[0], mean[1], mean[2]},
                        float3{stdv[0], stdv[1], stdv[2]});
+    ODAM_HIP(hipGetLastError());
+    return 0;
+}
+
+// The same resize, written as what the stem's bf16-plane contraction reads (detr_forward.hip stem_u8): the framed NHWC4 image
+// [B][H + 6][W + 8] of four bf16 per pixel, (u0 - c0, u1 - c1, u2 - c2, 1) inside the image and four zeros in the frame.  The
+// differences are integers in [-255, 255], exact in bf16 (top 16 bits of their fp32 form); the fourth channel tells conv1's folded
+// filters that the pixel exists (detr_weights.hip stem_u8_filters).  One thread per framed pixel, one 8-byte store: the grid covers
+// the frame, so nothing needs clearing and nothing stale is read.
+__global__ __launch_bounds__(256) void preprocess_u8_bf16x4_framed_kernel(const unsigned char* __restrict__ rgb, int h, int w,
+                                                                          ResampleTable tx, ResampleTable ty, int need_x, int need_y,
+                                                                          uint2* __restrict__ out, int H, int W, int c0, int c1, int c2) {
+    const int Xp = blockIdx.x * 256 + threadIdx.x;
+    const int Yp = blockIdx.y;
+    const size_t b = blockIdx.z;
+    if (Xp >= W + 8) return;
+    int X, Y;
+    uint2 v = uint2{0u, 0u};
+    if (odam_dm::stem_u8_inside(Xp, Yp, H, W, X, Y)) {
+        int u0, u1, u2;
+        resample_u8_pixel(rgb + b * (size_t)h * w * 3, w, tx, ty, need_x, need_y, X, Y, u0, u1, u2);
+        odam_dm::stem_u8_pixel(u0, u1, u2, c0, c1, c2, v.x, v.y);
+    }
+    out[(b * (H + 6) + Yp) * (size_t)(W + 8) + Xp] = v;
+}
+
+int launch_preprocess_u8_bf16x4_framed(const unsigned char* rgb, int B, int h, int w, const int* tx_xmin, const int* tx_cnt,
+                                       const int* tx_K, int tx_ksize, const int* ty_xmin, const int* ty_cnt, const int* ty_K,
+                                       int ty_ksize, void* out, int H, int W, const int centre[3], hipStream_t stream) {
+    if (B <= 0) return 0;
+    ResampleTable tx{tx_xmin, tx_cnt, tx_K, tx_ksize}, ty{ty_xmin, ty_cnt, ty_K, ty_ksize};
+    hipLaunchKernelGGL(preprocess_u8_bf16x4_framed_kernel, dim3((W + 8 + 255) / 256, H + 6, B), dim3(256), 0, stream, rgb, h, w, tx, ty,
+                       (int)(W != w), (int)(H != h), (uint2*)out, H, W, centre[0], centre[1], centre[2]);
     ODAM_HIP(hipGetLastError());
     return 0;
 }

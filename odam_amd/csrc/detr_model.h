@@ -144,6 +144,13 @@ struct odam_detr {
     struct Resample { int* xmin; int* cnt; int* K; int ksize; };
     std::map<std::pair<int, int>, Resample> resample;
 
+    // conv1 on raw uint8 frames (detr_forward.hip stem_from_u8, odam_config stem.u8): conv1's fp32 filters as loaded, and per (mean, std)
+    // pair seen the integer centres and the folded, pre-split filters (detr_weights.hip stem_u8_filters)
+    struct StemU8 { float mean[3], stdv[3]; int centre[3]; void* w3; };
+    std::vector<float> conv1_w;
+    std::vector<StemU8> stem_u8;
+    float* u8_img = nullptr;       // where that path does not apply: the normalised fp32 image [max_batch, 3, img_h, img_w], allocated on first use
+
     template <typename T>
     int dev_alloc(T** p, size_t n) {
         ODAM_HIP(hipMalloc((void**)p, n * sizeof(T)));
@@ -165,6 +172,17 @@ namespace odam_dm {
 odam_cg::ConvGemmArgs conv_args(const Conv& c, const void* x, int B, int H, int W, int dtype);
 // the same for an mxfp8 body layer (cg_mx8.h); the caller sets the residual, the outputs and the ReLU
 odam_mx::ConvArgs mx_args(const Conv& c, const void* x, const void* xs, int B, int H, int W);
+
+// detr_weights.hip: conv1 [Cout][3][7][7] as the row-convolution stem (m->stem_rows); the filters of the uint8 stem for one (mean, std) pair
+int pack_stem_rows(odam_detr* m, const float* w, int Cout, float* scale, float* bias);
+int stem_u8_filters(odam_detr* m, const float* mean, const float* stdv, const odam_detr::StemU8** out);
+// detr_input.hip: the two resampling tables of an h x w frame for this model's input size
+int resample_tables(odam_detr* m, int h, int w, odam_detr::Resample* tx, odam_detr::Resample* ty);
+// detr_forward.hip: conv1 + bn1 + ReLU + max-pool from raw uint8 frames [B, h, w, 3] into m->bufA [B, H2, W2, 64]: on the centred bf16 frame
+// where that applies (*path = 1; path nullable), else through the normalised fp32 image and the stem as odam_detr_forward runs it (*path = 0)
+int stem_from_u8(odam_detr* m, const unsigned char* rgb, int B, int h, int w, const float* mean, const float* stdv, hipStream_t st, int* path);
+// ... and whether conv1 would run as the row convolution at all for B frames (the op-level entry has no other stem to fall back to)
+bool stem_rows_applies(const odam_detr* m, int B);
 
 // one layer on conv_gemm: y = act(conv(x) * scale + bias + res)
 int run_conv(const Conv& c, const void* x, int B, int H, int W, const void* res, bool relu, void* y, hipStream_t st,

@@ -226,6 +226,34 @@ extern "C" int odam_op_bottleneck_f32(const float* x, const float* w2, const flo
     return rc;
 }
 
+// ---- the stem from raw frames: a model of nothing but conv1, built for the call ----
+extern "C" int odam_op_stem_u8(const unsigned char* rgb, int B, int h, int w, int H, int W, const float* conv1_w, const float* scale,
+                               const float* bias, const float* mean, const float* std_dev, float* y, int* path, void* stream) {
+    const char* who = "odam_op_stem_u8";
+    if (!rgb || !conv1_w || !scale || !bias || !mean || !std_dev || !y) return fail(1, who, "null pointer");
+    if (B < 1 || h < 1 || w < 1 || H < 32 || W < 32) return fail(1, who, "bad size");
+    hipStream_t st = (hipStream_t)stream;
+    odam_detr m{};
+    m.cfg.img_h = H; m.cfg.img_w = W; m.cfg.max_batch = B;
+    m.H1 = conv_out(H, 7, 2, 3); m.W1 = conv_out(W, 7, 2, 3);
+    m.H2 = conv_out(m.H1, 3, 2, 1); m.W2 = conv_out(m.W1, 3, 2, 1);
+    auto run = [&]() -> int {
+        RC(pack_stem_rows(&m, conv1_w, 64, const_cast<float*>(scale), const_cast<float*>(bias)));
+        if (!stem_rows_applies(&m, B)) return fail(4, who, "conv1 does not run as the row convolution here");
+        RC(m.dev_alloc(&m.x4, (size_t)B * (H + 6) * (W + 8) * 16));
+        RC(m.dev_alloc(&m.stem_out, (size_t)B * m.H1 * m.W1 * 64 * 4));
+        m.bufA = reinterpret_cast<char*>(y);
+        int p = 0;
+        RC(stem_from_u8(&m, rgb, B, h, w, mean, std_dev, st, &p));
+        if (path) *path = p;
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(st);
+    for (void* p : m.allocs) (void)hipFree(p);
+    return rc;
+}
+
 extern "C" long long odam_op_conv_paths(char* buf, int n, int reset) { return odam_cg::read_paths(buf, n, reset); }
 
 // experiment switch of the bf16-native contraction kernel (cg_choice.h set_big_mode): 0 off, 1 auto, 2 whenever eligible

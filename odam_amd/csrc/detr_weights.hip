@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "detr_model.h"
+#include "stem_u8_fold.h"
 
 using namespace odam_dm;
 
@@ -167,6 +168,49 @@ int check_shape(const HostTensor& w, int cout, int cin, int k, const std::string
 
 }  // namespace
 
+namespace odam_dm {
+
+// conv1 as KH = 7, KW = 1, Cin = 32: filter row ky of output channel o is the 28 values w[o][c][ky][kx] at position 4 kx + c (what 7
+// consecutive NHWC4 pixels hold), then 4 zeros; K = 7 * 32 = 224.  fp32: k_order 1 (one 32-channel chunk); bf16: the k-tile is 32
+// elements = one filter row, tap-major (k_order 0).  Keeps w for the filters of the uint8 stem (stem_u8_filters)
+int pack_stem_rows(odam_detr* m, const float* w, int Cout, float* scale, float* bias) {
+    const int Kp = m->dt ? 256 : 224;          // bf16: the dispatcher's k-tile is 64 elements (an eighth, all-zero filter row)
+    std::vector<float> pr((size_t)Cout * Kp, 0.0f);
+    for (int o = 0; o < Cout; o++)
+        for (int ci = 0; ci < 3; ci++)
+            for (int ky = 0; ky < 7; ky++)
+                for (int kx = 0; kx < 7; kx++)
+                    pr[(size_t)o * Kp + ky * 32 + kx * 4 + ci] = w[(((size_t)o * 3 + ci) * 7 + ky) * 7 + kx];
+    Conv& r = m->stem_rows;
+    r.Cin = 32; r.Cout = Cout; r.KH = 7; r.KW = 1; r.stride = 2; r.pad = 0; r.Kpad = Kp; r.k_order = m->dt ? 0 : 1;
+    RC(upload_w3(m, &r.w3, pr, Cout, Kp));
+    RC(upload_w(m, &r.w, pr));
+    r.scale = scale; r.bias = bias;
+    if (m->dt == 0) m->conv1_w.assign(w, w + (size_t)Cout * 147);
+    return 0;
+}
+
+// conv1's filters for the centred uint8 frame (stem_u8_fold.h), split into the three bf16 planes of the split contraction mode:
+// built on first use for a (mean, std) pair and kept on the model, as the resampling tables are
+int stem_u8_filters(odam_detr* m, const float* mean, const float* stdv, const odam_detr::StemU8** out) {
+    for (const odam_detr::StemU8& f : m->stem_u8)
+        if (std::memcmp(f.mean, mean, 12) == 0 && std::memcmp(f.stdv, stdv, 12) == 0) { *out = &f; return 0; }
+    const int Cout = m->stem_rows.Cout;
+    if (m->conv1_w.size() != (size_t)Cout * 147 || m->stem_rows.Kpad != 224) return odam_fail(1, "stem_u8_filters: no fp32 conv1 filters on this model");
+    odam_detr::StemU8 f{};
+    std::memcpy(f.mean, mean, 12); std::memcpy(f.stdv, stdv, 12);
+    stem_u8_centres(mean, f.centre);
+    std::vector<float> rows((size_t)Cout * 224);
+    stem_u8_fold(m->conv1_w.data(), Cout, mean, stdv, rows.data());
+    RC(upload_w3(m, &f.w3, rows, Cout, 224));
+    if (!f.w3) return odam_fail(1, "stem_u8_filters: the split filters could not be built");
+    m->stem_u8.push_back(f);      // (the pointer handed out serves the one call that asked: a later pair may move the entries)
+    *out = &m->stem_u8.back();
+    return 0;
+}
+
+}  // namespace odam_dm
+
 extern "C" int odam_detr_create(const odam_detr_cfg* cfg, odam_detr** out) {
     if (!cfg || !out) return odam_fail(1, "odam_detr_create: null argument");
     // transformer widths: the attention kernels take head dim 32 or 64, the LayerNorm kernels 64 n channels, n = 2 .. 16
@@ -237,24 +281,9 @@ extern "C" int odam_detr_finalize(odam_detr* m) {
         NEED(w, bb + "conv1.weight");
         RC(pack_conv(m, m->stem, *w, 2, 3));
         RC(fold_bn(m, m->stem, bb + "bn1"));
-        {
-            // conv1 as KH = 7, KW = 1, Cin = 32: filter row ky of output channel o is the 28 values w[o][c][ky][kx] at
-            // position 4 kx + c (what 7 consecutive NHWC4 pixels hold), then 4 zeros; K = 7 * 32 = 224.  fp32: k_order 1 (one
-            // 32-channel chunk); bf16: the k-tile is 32 elements = one filter row, tap-major (k_order 0)
-            const int Cout = (int)w->shape[0];
-            const int Kp = m->dt ? 256 : 224;          // bf16: the dispatcher's k-tile is 64 elements (an eighth, all-zero filter row)
-            std::vector<float> pr((size_t)Cout * Kp, 0.0f);
-            for (int o = 0; o < Cout; o++)
-                for (int ci = 0; ci < 3; ci++)
-                    for (int ky = 0; ky < 7; ky++)
-                        for (int kx = 0; kx < 7; kx++)
-                            pr[(size_t)o * Kp + ky * 32 + kx * 4 + ci] = w->data[(((size_t)o * 3 + ci) * 7 + ky) * 7 + kx];
-            Conv& r = m->stem_rows;
-            r.Cin = 32; r.Cout = Cout; r.KH = 7; r.KW = 1; r.stride = 2; r.pad = 0; r.Kpad = Kp; r.k_order = m->dt ? 0 : 1;
-            RC(upload_w3(m, &r.w3, pr, Cout, Kp));
-            RC(upload_w(m, &r.w, pr));
-            r.scale = m->stem.scale; r.bias = m->stem.bias;
-        }
+        if (w->shape.size() != 4 || w->shape[1] != 3 || w->shape[2] != 7 || w->shape[3] != 7)
+            return odam_fail(1, "odam_detr_finalize: backbone.0.body.conv1.weight must be [Cout, 3, 7, 7]");
+        RC(pack_stem_rows(m, w->data.data(), (int)w->shape[0], m->stem.scale, m->stem.bias));
     }
     int inplanes = 64;
     for (int l = 0; l < 4; l++) {

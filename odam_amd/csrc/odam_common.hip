@@ -23,6 +23,7 @@ const Entry TABLE[N_KEYS] = {
     {"assoc.hungarian", 0, 0, 1},
     {"assoc.merge", 1, 0, 1},
     {"sq.two_per_cu", 1, 0, 1},
+    {"stem.u8", 1, 0, 1},
 };
 std::atomic<int> g_val[N_KEYS];
 std::atomic<bool> g_init{false};

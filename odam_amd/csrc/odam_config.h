@@ -47,6 +47,10 @@ enum Key {
     SQ_TWO_PER_CU,  // super-quadric fit, launches of more objects than CUs (one workgroup per object, no view split): 1 (default) = read the view counts
                     // back and either fit the objects longest first (unequal view counts: the launch ends with the last long object) or, for about
                     // equal ones, run 512-thread workgroups two per CU (500 x 256: 29 -> 24 ms per launch, 300 x 128 -17 %).  Same bits.  0 = neither
+    STEM_U8,        // raw uint8 frames (odam_detr_forward_u8), fp32 split mode: 1 = conv1 reads the resized frame as centred integers in ONE bf16 plane
+                    // (8 bytes per pixel, written framed by the resize itself) with the normalisation folded into its filters: three products per
+                    // block instead of six, none dropped, no fp32 image and no layout pass.  Last bits differ from 0 = the normalised fp32 image
+                    // (what odam_detr_preprocess_u8 + odam_detr_forward compute, bit for bit)
     N_KEYS
 };
 int get(Key k);

@@ -159,7 +159,7 @@ class Detector:
         new = torch.device("cuda:0" if str(device) == "cuda" else device)
         if new != self.device:
             self.close()          # handles, streams and scratch belong to the old device
-            for name in ("_streams", "_mscratch", "_xform", "_stage", "_copy_stream", "_pinned"):
+            for name in ("_streams", "_mscratch", "_stage", "_copy_stream", "_pinned"):
                 if hasattr(self, name):
                     setattr(self, name, None)
         self.device = new
@@ -372,14 +372,34 @@ class Detector:
                                                           ctypes.c_void_p(st)), "odam_detr_preprocess_u8")
         return out
 
+    def _forward_raw(self, handle, rgb, outs, stream):
+        """odam_detr_forward_u8 on one batch (<= max_batch) of raw frames: the input transform and the forward as one call of the library,
+        which reads the resized frame as integers where its conv1 can (odam_config stem.u8); outs = the six pred_* tensors + features or None"""
+        from .transforms import MEAN, STD
+        B, h, w, c = rgb.shape
+        assert c == 3 and rgb.dtype == torch.uint8 and rgb.is_cuda and rgb.is_contiguous()
+        mean, std = (ctypes.c_float * 3)(*MEAN), (ctypes.c_float * 3)(*STD)
+        ad = lambda t: None if t is None else t.data_ptr()
+        _lib.check(_lib.lib().odam_detr_forward_u8(handle, rgb.data_ptr(), B, h, w, ctypes.addressof(mean), ctypes.addressof(std),
+                                                   *[ad(t) for t in outs], stream), "odam_detr_forward_u8")
+
     def forward_u8(self, rgb):
-        """raw uint8 [B,h,w,3] frames (device) -> the DETR output dict; B <= max_batch per preprocessing call"""
-        outs = [self(self.preprocess_u8(rgb[b0:b0 + self.max_batch])) for b0 in range(0, rgb.shape[0], self.max_batch)]
-        if len(outs) == 1:
-            return outs[0]
-        res = {k: torch.cat([o[k] for o in outs]) for k in outs[0] if k != "_hw"}
-        res["_hw"] = outs[0]["_hw"]
-        return res
+        """raw uint8 [B,h,w,3] frames (device) -> the DETR output dict"""
+        from .transforms import target_size
+        N, h, w, _ = rgb.shape
+        H, W = target_size(w, h, *self.resize)
+        a, dev = self.arch, self.device
+        mk = lambda n: torch.empty(N, a["num_queries"], n, device=dev, dtype=torch.float32)
+        out = {"pred_logits": mk(a["num_classes1"]), "pred_boxes": mk(4), "pred_angle": mk(a["angle_bins"]),
+               "pred_offset": mk(2), "pred_size": mk(3), "pred_depth": mk(1), "pred_obj_features": mk(a["hidden_dim"])}
+        keys = ("pred_logits", "pred_boxes", "pred_angle", "pred_offset", "pred_size", "pred_depth", "pred_obj_features")
+        handle = self._handle(H, W)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            for b0 in range(0, N, self.max_batch):
+                self._forward_raw(handle, rgb[b0:b0 + self.max_batch], [out[k][b0:b0 + self.max_batch] for k in keys], st)
+        out["_hw"] = (H, W)
+        return out
 
     def debug_taps(self, B, H, W):
         """layer4 feature map [B,C4,h,w] (C4 = 2048 Bottleneck, 512 BasicBlock backbones) and encoder memory [B,h*w,hidden_dim] of the
@@ -549,9 +569,6 @@ class Detector:
         events = []
         nb = 0
         on_host = not frames.is_cuda
-        if raw:
-            if getattr(self, "_xform", None) is None or self._xform[0].shape[2:] != (H, W) or len(self._xform) != ns:
-                self._xform = [torch.empty(mb, 3, H, W, device=dev, dtype=torch.float32) for _ in range(ns)]
         if on_host:
             st0 = getattr(self, "_stage", None)
             if st0 is None or st0[0][0].shape[1:] != frames.shape[1:] or st0[0][0].dtype != frames.dtype or len(st0) != ns:
@@ -582,11 +599,12 @@ class Detector:
                             up.record(self._copy_stream)
                         self._streams[k].wait_event(up)
                         src = buf
-                    if raw:    # same stream as the forward that reads it: the buffer is free again when that is done
-                        src = self.preprocess_u8(src, self._xform[k][:B], k, self._streams[k].cuda_stream)
-                    _lib.check(L.odam_detr_forward(handles[k], _lib.ptr(src), ctypes.c_int(B), _lib.ptr(lg),
-                                                   _lib.ptr(bx), _lib.ptr(an), _lib.ptr(of), _lib.ptr(sz), _lib.ptr(dp),
-                                                   ctypes.c_void_p(0), sp), "odam_detr_forward")
+                    if raw:    # the input transform and the forward as one call: the library keeps whatever image it builds in between
+                        self._forward_raw(handles[k], src, [t[:B] for t in (lg, bx, an, of, sz, dp)] + [None], self._streams[k].cuda_stream)
+                    else:
+                        _lib.check(L.odam_detr_forward(handles[k], _lib.ptr(src), ctypes.c_int(B), _lib.ptr(lg),
+                                                       _lib.ptr(bx), _lib.ptr(an), _lib.ptr(of), _lib.ptr(sz), _lib.ptr(dp),
+                                                       ctypes.c_void_p(0), sp), "odam_detr_forward")
                     _lib.check(L.odam_detr_postprocess(handles[k], _lib.ptr(lg), _lib.ptr(bx), _lib.ptr(an), _lib.ptr(of),
                                                        _lib.ptr(sz), _lib.ptr(dp), ctypes.c_int(B),
                                                        K9.ctypes.data_as(_lib.c_float_p), ctypes.c_float(img_w),
