@@ -303,6 +303,37 @@ int odam_sq_prepare_batch(odam_sq_ctx* ctx, int n_obj, const int* row_off, const
                           double* pose, double* bboxes_dl, int* status, int* view_img, int* view_row, float* tgt, float* mask,
                           float* P, int* valid, void* stream);
 
+/*
+ * odam_sq_prepare_batch for the tracks of MANY scenes in one launch: the single image table and image size become one per scene.
+ * Still one workgroup per track; it finds its scene in trk_off (a binary search on the workgroup's index) and searches that scene's
+ * slice of img_ids only.  Every output word is the word odam_sq_prepare_batch writes when it is called on that scene alone; view_img
+ * stays the image index INSIDE the scene, per-view words still start at row_off[o], status codes and their precedence are the same.
+ * Stream-ordered, no synchronisation, no allocation, no device-wide barrier.
+ *   n_scene                         scenes (>= 1 where there is a track)
+ *   trk_off      [dev] [n_scene+1]  scene s owns tracks trk_off[s] .. trk_off[s+1]-1 (trk_off[0] = 0, trk_off[n_scene] = n_obj, not
+ *                                   decreasing; an empty scene is legal).  A track no scene owns has no image: status 1
+ *   img_off      [dev] [n_scene+1]  scene s owns entries img_off[s] .. img_off[s+1]-1 of img_ids, img_order and P_cws, the scenes' tables
+ *                                   one after the other; a slice that does not lie inside 0 .. n_img is taken as empty
+ *   n_img                           entries of the concatenated tables
+ *   img_ids      [dev] [n_img]      ascending and all different inside every scene's slice; the same id may appear in several scenes
+ *   img_order    [dev] [n_img]      image index of img_ids[i] inside its scene, 0 .. (images of the scene) - 1
+ *   P_cws        [dev] [n_img][12]  projection of image j of scene s at entry img_off[s] + j
+ *   img_wh       [dev] [n_scene][2] float64 (img_w, img_h) of every scene
+ *   scene_rows   [dev] [n_scene]    nullable.  The max_rows odam_sq_prepare_batch would be given for scene s alone.  That call sizes its
+ *                                   workgroups from max_rows, the size decides how a track's sorted rows are dealt to the threads, and that
+ *                                   the order of the sin / cos sums behind the yaw; with scene_rows a workgroup deals them as the launch
+ *                                   for its scene would (and refuses tracks as it would: status 3 beyond the power of two that holds
+ *                                   scene_rows[s]), so the yaw has that launch's bits.  Values above max_rows are taken as max_rows.  Null:
+ *                                   every scene as a launch with this call's max_rows
+ * Everything else as odam_sq_prepare_batch.
+ */
+int odam_sq_prepare_scenes(odam_sq_ctx* ctx, int n_obj, const int* row_off, const double* rows, int max_rows, int n_scene,
+                           const int* trk_off, const int* img_off, int n_img, const long long* img_ids, const int* img_order,
+                           const double* P_cws, const double* img_wh, const int* scene_rows, double thr, int representation, int* cls,
+                           int* n_obs,
+                           int* n_valid, float* init, float* half_dims, double* pose, double* bboxes_dl, int* status,
+                           int* view_img, int* view_row, float* tgt, float* mask, float* P, int* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@
 // sums of sin / cos that decide the yaw are a per-thread, per-wave (XOR butterfly), per-workgroup (wave order) reduction: fixed, so
 // results repeat from launch to launch, but not the order of a host sum.  The class is a median over integers 0..63: a histogram.
 // Compiled with -ffp-contract=off: every product and sum is rounded on its own.
+//
+// odam_sq_prepare_scenes is the same kernel instantiated with SCENES: the tracks of many scenes in one launch, every workgroup on its
+// own scene's image tables and image size.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -39,6 +42,12 @@ struct PrepArgs {
     const double* P_cws;
     int n_obj, n_img, cap, representation;      // cap: keys the launch's LDS holds
     double img_w, img_h, thr;
+    // odam_sq_prepare_scenes only: the tracks of n_scene scenes, every scene with its own slice of the image tables and its own image size
+    int n_scene;
+    const int* trk_off;
+    const int* img_off;
+    const double* img_wh;
+    const int* scene_rows;      // nullable: per scene, the max_rows a launch for that scene alone would have been given
     int *cls, *n_obs, *n_valid;
     float *init, *half_dims;
     double *pose, *bboxes_dl;
@@ -48,6 +57,13 @@ struct PrepArgs {
     int* valid;
 };
 
+// SCENES: the workgroup first finds the scene its track belongs to (trk_off, a wave-uniform binary search: blockIdx only) and takes that
+// scene's slice of img_ids / img_order / P_cws and its image size; everything after that is the single-scene kernel on that slice, so
+// every word is the word odam_sq_prepare_batch writes for the scene alone.  Without SCENES the slice is the whole table.
+// The order of the sin / cos sums follows from how the sorted entries are dealt to the threads, and that from the size the launch was
+// given (threads = cap / 2).  With scene_rows the workgroup deals them as the launch for its scene alone would -- to the first `own`
+// threads, the others hold no entry and add zeros -- so the yaw too has that launch's bits, whatever size this launch has.
+template <bool SCENES>
 __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     __shared__ int s_hist[N_CLASS];
@@ -60,15 +76,42 @@ __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
     const int obj = blockIdx.x;
     const int tid = threadIdx.x, T = blockDim.x;
     const int lane = tid & 63, wave = tid >> 6, n_waves = T >> 6;
+    int i0 = 0, n_img = A.n_img;      // the scene's slice of the image tables
+    double img_w = A.img_w, img_h = A.img_h;
+    int cap = A.cap, own = T;         // rows a track may have; threads that are dealt sorted entries
+    if constexpr (SCENES) {
+        int lo = 0, hi = A.n_scene;      // first scene whose tracks end behind obj (an empty scene never is)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (A.trk_off[mid + 1] <= obj) lo = mid + 1; else hi = mid;
+        }
+        i0 = 0; n_img = 0;               // a track no scene owns, or a slice outside the tables: no image, so no view
+        if (lo < A.n_scene) {
+            const int a = A.img_off[lo], b = A.img_off[lo + 1];
+            if (a >= 0 && b >= a && b <= A.n_img) { i0 = a; n_img = b - a; }
+            img_w = A.img_wh[2 * lo]; img_h = A.img_wh[2 * lo + 1];
+            if (A.scene_rows) {      // the launch shape of odam_sq_prepare_batch(max_rows = scene_rows[lo]), never beyond this launch's
+                const int m = A.scene_rows[lo];
+                int c = 1;
+                while (c < m && c < cap) c <<= 1;
+                cap = c;
+                own = c / 2;
+                own = own < 64 ? 64 : (own > T ? T : own);
+            }
+        }
+    }
+    const long long* img_ids = A.img_ids + i0;
+    const int* img_order = A.img_order + i0;
+    const double* P_cws = A.P_cws + (size_t)i0 * 12;
     const int r0 = A.row_off[obj];
     const int n = A.row_off[obj + 1] - r0;
     // both refusals are workgroup-uniform and come before any row is read
-    if (n > A.cap || n <= 0) {
+    if (n > cap || n <= 0) {
         if (tid == 0) {
             A.cls[obj] = -1;
             A.n_obs[obj] = 0;
             A.n_valid[obj] = 0;
-            A.status[obj] = n > A.cap ? ODAM_SQ_PREPARE_TOO_MANY_ROWS : ODAM_SQ_PREPARE_NO_VIEW;
+            A.status[obj] = n > cap ? ODAM_SQ_PREPARE_TOO_MANY_ROWS : ODAM_SQ_PREPARE_NO_VIEW;
         }
         return;
     }
@@ -87,14 +130,14 @@ __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
             const double f = rows[(size_t)i * 14 + 0];
             if (f > -2147483649.0 && f < 2147483648.0) {      // truncates into int32 (NaN fails both)
                 const long long id = (long long)(int)f;
-                int lo = 0, hi = A.n_img;                      // first entry >= id
+                int lo = 0, hi = n_img;                        // first entry >= id
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    if (A.img_ids[mid] < id) lo = mid + 1; else hi = mid;
+                    if (img_ids[mid] < id) lo = mid + 1; else hi = mid;
                 }
-                if (lo < A.n_img && A.img_ids[lo] == id) {
-                    const int img = A.img_order[lo];
-                    if (img >= 0 && img < A.n_img) key = view_key(img, i);
+                if (lo < n_img && img_ids[lo] == id) {
+                    const int img = img_order[lo];
+                    if (img >= 0 && img < n_img) key = view_key(img, i);
                 }
             }
             const double c = rows[(size_t)i * 14 + 1];
@@ -108,7 +151,7 @@ __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
     lds_bitonic_sort(keys, n2, tid, T);
 
     // every thread owns a run of L sorted entries; views in front of it = where its own views go
-    const int L = n2 > T ? n2 / T : 1;
+    const int L = n2 > own ? n2 / own : 1;      // (threads from `own` on start at or behind n2: they own nothing)
     const int j0 = tid * L;
     const int j1 = j0 < n ? (j0 + L < n ? j0 + L : n) : j0;      // entries past n are all ones
     int cnt = 0;
@@ -129,7 +172,7 @@ __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
     }
 
     // per-view outputs
-    const double lim[4] = {A.img_w, A.img_w, A.img_h, A.img_h};
+    const double lim[4] = {img_w, img_w, img_h, img_h};
     const int col[4] = {2, 4, 3, 5};      // x_min, x_max, y_min, y_max
     int my_valid = 0;
     double my_sin = 0.0, my_cos = 0.0;
@@ -150,7 +193,7 @@ __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
             any = any || m;
         }
 #pragma unroll
-        for (int k = 0; k < 12; k++) A.P[g * 12 + k] = (float)A.P_cws[(size_t)img * 12 + k];
+        for (int k = 0; k < 12; k++) A.P[g * 12 + k] = (float)P_cws[(size_t)img * 12 + k];
         A.view_img[g] = img;
         A.view_row[g] = i;
         A.valid[g] = any ? 1 : 0;
@@ -266,6 +309,22 @@ __global__ __launch_bounds__(1024) void sq_prepare_kernel(PrepArgs A) {
     }
 }
 
+// sizes the workgroup and its LDS from max_rows and launches one workgroup per track
+template <bool SCENES>
+int launch_prepare(PrepArgs& A, int max_rows, hipStream_t stream) {
+    int cap = 1;
+    while (cap < max_rows && cap < ODAM_SQ_PREPARE_MAX_ROWS) cap <<= 1;
+    int threads = cap / 2;
+    threads = threads < 64 ? 64 : (threads > 1024 ? 1024 : threads);
+    const size_t lds = sizeof(unsigned long long) * (size_t)cap;
+    if (lds > 48 * 1024)
+        ODAM_HIP(hipFuncSetAttribute((const void*)sq_prepare_kernel<SCENES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    A.cap = cap;
+    hipLaunchKernelGGL(sq_prepare_kernel<SCENES>, dim3((unsigned)A.n_obj), dim3((unsigned)threads), lds, stream, A);
+    ODAM_HIP(hipGetLastError());
+    return ODAM_OK;
+}
+
 }  // namespace
 
 extern "C" int odam_sq_prepare_batch(odam_sq_ctx* ctx, int n_obj, const int* row_off, const double* rows, int max_rows, int n_img,
@@ -282,20 +341,36 @@ extern "C" int odam_sq_prepare_batch(odam_sq_ctx* ctx, int n_obj, const int* row
         return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_batch: half_dims is null for the dual quadric");
     if (n_obj < 0 || n_img < 0 || max_rows < 1) return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_batch: bad size");
     if (n_obj == 0) return ODAM_OK;
-    int cap = 1;
-    while (cap < max_rows && cap < ODAM_SQ_PREPARE_MAX_ROWS) cap <<= 1;
-    int threads = cap / 2;
-    threads = threads < 64 ? 64 : (threads > 1024 ? 1024 : threads);
-    const size_t lds = sizeof(unsigned long long) * (size_t)cap;
-    if (lds > 48 * 1024)
-        ODAM_HIP(hipFuncSetAttribute((const void*)sq_prepare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PrepArgs A{};
     A.row_off = row_off; A.rows = rows; A.img_ids = img_ids; A.img_order = img_order; A.P_cws = P_cws;
-    A.n_obj = n_obj; A.n_img = n_img; A.cap = cap; A.representation = representation;
+    A.n_obj = n_obj; A.n_img = n_img; A.representation = representation;
     A.img_w = img_w; A.img_h = img_h; A.thr = thr;
     A.cls = cls; A.n_obs = n_obs; A.n_valid = n_valid; A.init = init; A.half_dims = half_dims; A.pose = pose; A.bboxes_dl = bboxes_dl;
     A.status = status; A.view_img = view_img; A.view_row = view_row; A.tgt = tgt; A.mask = mask; A.P = P; A.valid = valid;
-    hipLaunchKernelGGL(sq_prepare_kernel, dim3((unsigned)n_obj), dim3((unsigned)threads), lds, (hipStream_t)stream, A);
-    ODAM_HIP(hipGetLastError());
-    return ODAM_OK;
+    return launch_prepare<false>(A, max_rows, (hipStream_t)stream);
+}
+
+extern "C" int odam_sq_prepare_scenes(odam_sq_ctx* ctx, int n_obj, const int* row_off, const double* rows, int max_rows, int n_scene,
+                                      const int* trk_off, const int* img_off, int n_img, const long long* img_ids, const int* img_order,
+                                      const double* P_cws, const double* img_wh, const int* scene_rows, double thr, int representation, int* cls, int* n_obs,
+                                      int* n_valid, float* init, float* half_dims, double* pose, double* bboxes_dl, int* status,
+                                      int* view_img, int* view_row, float* tgt, float* mask, float* P, int* valid, void* stream) {
+    if (!ctx || !row_off || !rows || !trk_off || !img_off || !img_ids || !img_order || !P_cws || !img_wh || !cls || !n_obs || !n_valid ||
+        !init || !pose || !bboxes_dl || !status || !view_img || !view_row || !tgt || !mask || !P || !valid)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_scenes: null pointer");
+    if (representation < 0 || representation > ODAM_SQ_DUAL_QUADRIC)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_scenes: representation outside 0..3");
+    if (representation == ODAM_SQ_DUAL_QUADRIC && !half_dims)
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_scenes: half_dims is null for the dual quadric");
+    if (n_obj < 0 || n_scene < 0 || n_img < 0 || max_rows < 1 || (n_obj > 0 && n_scene < 1))
+        return odam_fail(ODAM_E_INVALID, "odam_sq_prepare_scenes: bad size");
+    if (n_obj == 0) return ODAM_OK;
+    PrepArgs A{};
+    A.row_off = row_off; A.rows = rows; A.img_ids = img_ids; A.img_order = img_order; A.P_cws = P_cws;
+    A.n_obj = n_obj; A.n_img = n_img; A.representation = representation;
+    A.thr = thr;
+    A.n_scene = n_scene; A.trk_off = trk_off; A.img_off = img_off; A.img_wh = img_wh; A.scene_rows = scene_rows;
+    A.cls = cls; A.n_obs = n_obs; A.n_valid = n_valid; A.init = init; A.half_dims = half_dims; A.pose = pose; A.bboxes_dl = bboxes_dl;
+    A.status = status; A.view_img = view_img; A.view_row = view_row; A.tgt = tgt; A.mask = mask; A.P = P; A.valid = valid;
+    return launch_prepare<true>(A, max_rows, (hipStream_t)stream);
 }

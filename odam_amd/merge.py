@@ -251,6 +251,86 @@ def merge_packed(data, img_names, fitter=None, rows=None):
             "src": res["out_src"][:r_out]}
 
 
+def merge_packed_scenes(datas, img_names_list, fitter=None, rows=None):
+    """merge_packed for MANY scenes whose rows are on the device already: _device_merge's three steps in the launches of one scene --
+    ONE IoU launch, ONE merge_cluster, ONE merge_assemble(want_rows14=True), ONE small copy back (the head).
+    rows: the combined packed block of the scenes' tracks (track_store.pack_scenes: "rows14", "row_offsets", "trk_off"), one scene
+    per entry of datas.  Returns (block, scenes):
+      block   {"rows14" [R_out, 14], "row_offsets" [n_total + 1] int32, "cls" [n_total] int32, "src" [R_out] int32} on the device: the
+              merged tracks of all scenes that went to the device, one scene after the other in the order of datas, and on the host
+              "n_out" [S] (merged tracks per scene; 0 for a scene that did not go), "status" [S] (-1 for a scene _device_scene refuses),
+              "row_base" [S] (what "src" of the scene's rows counts from: its first row among the rows that went).  None where no scene went.
+      scenes  per scene None -- _device_scene refuses it, or it came back with a status: the caller's host path -- or the scene's own
+              merge_packed dict, sliced out of the block LAZILY: a callable without arguments (the slices cost two small launches a
+              scene, which a caller that adopts the whole block -- track_store.adopt_scenes, tracks_from_packed_scenes -- never pays)."""
+    import torch
+    from . import evaluate
+    if rows is None:
+        raise ValueError("merge_packed_scenes: rows= the combined packed block of the scenes (track_store.pack_scenes)")
+    if len(datas) != len(img_names_list):
+        raise ValueError("one list of image names per scene")
+    trk = np.asarray(rows["trk_off"], np.int64)
+    off = np.asarray(rows["row_offsets"], np.int64)
+    S = len(datas)
+    if len(trk) != S + 1:
+        raise ValueError(f"merge: the packed block of rows holds {len(trk) - 1} scenes, {S} were given")
+    fitter = evaluate._default_fitter(fitter)
+    scenes = [_device_scene(d, names) for d, names in zip(datas, img_names_list)]
+    picked = [k for k, s in enumerate(scenes) if s is not None]
+    for k in picked:
+        if not np.array_equal(np.diff(off[trk[k]:trk[k + 1] + 1]), [len(t) for t in scenes[k][0]]):
+            raise ValueError(f"merge: the packed block of rows does not hold the tracks of scene {k} (rows per track differ)")
+    if not picked:
+        return None, [None] * S
+    r = evaluate._iou_launch([scenes[k][2] for k in picked], [scenes[k][2] for k in picked], [scenes[k][3] for k in picked],
+                             [scenes[k][3] for k in picked], 2, fitter, False)
+    cl = fitter.merge_cluster(r["iou3d"], r["a_off"], r["pair_off"])
+    if len(picked) == S:
+        rows14, row_off = rows["rows14"], off
+    else:      # the scenes that went, device to device
+        rows14 = torch.cat([rows["rows14"][int(off[trk[k]]):int(off[trk[k + 1]])] for k in picked])
+        row_off = np.concatenate([[0], np.cumsum(np.concatenate([np.diff(off[trk[k]:trk[k + 1] + 1]) for k in picked]))])
+    res = fitter.merge_assemble(cl, r["a_off"], rows14, row_off, [img_names_list[k] for k in picked], want_rows14=True)
+    head = res["head"].cpu().numpy()
+    ns = len(picked)
+    n_total, r_total = int(head[2 * ns]), int(head[2 * ns + 1])
+    n_out, status, row_base = np.zeros(S, np.int64), np.full(S, -1, np.int64), np.zeros(S, np.int64)
+    base = 0
+    for q, k in enumerate(picked):
+        n_out[k], status[k], row_base[k] = int(head[q]), int(head[ns + q]), base
+        base += int(off[trk[k + 1]] - off[trk[k]])
+    block = {"rows14": res["rows14"][:r_total], "row_offsets": res["out_off"][:n_total + 1], "cls": res["out_cls"][:n_total],
+             "src": res["out_src"][:r_total], "n_out": n_out, "status": status, "row_base": row_base}
+    first = np.concatenate([[0], np.cumsum(n_out)])
+
+    def one(k):
+        def cut():      # merge_packed's dict for scene k; the two row bounds are the only words read back
+            o = block["row_offsets"][int(first[k]):int(first[k + 1]) + 1]
+            a, b = (int(x) for x in o[[0, -1]].cpu().numpy())
+            return {"rows14": block["rows14"][a:b], "row_offsets": o - a, "cls": block["cls"][int(first[k]):int(first[k + 1])],
+                    "src": block["src"][a:b] - int(row_base[k])}
+        return cut
+    return block, [one(k) if status[k] == 0 else None for k in range(S)]
+
+
+def tracks_from_packed_scenes(block, datas):
+    """tracks_from_packed for every scene of merge_packed_scenes' block with ONE small copy back: per scene the merged [n, 82] host
+    tracks gathered from datas[k]["tracks"], or None for a scene that did not come back merged (status != 0)."""
+    import torch
+    n, r = int(block["cls"].shape[0]), int(block["src"].shape[0])
+    h = torch.cat([block["row_offsets"].to(torch.int32), block["src"].to(torch.int32), block["cls"].to(torch.int32)]).cpu().numpy()
+    off, src, cls = h[:n + 1], h[n + 1:n + 1 + r], h[n + 1 + r:]
+    out, o = [], 0
+    for k, data in enumerate(datas):
+        k_out = int(block["n_out"][k])
+        if block["status"][k] == 0:
+            out.append(_gather_merged(data["tracks"], off[o:o + k_out + 1], src, cls[o:o + k_out], int(block["row_base"][k])))
+        else:
+            out.append(None)
+        o += k_out
+    return out
+
+
 def merge_process(data, img_names, fitter=None, on_device=False):
     """run_merge.py:79-130: data = optim_process output dict; returns the list of merged [n,82] tracks.  With a fitter the pair
     costs come from the device (cost_matrix); with on_device the clustering and the assembly too (merge_scenes: the same tracks,

@@ -561,6 +561,101 @@ def optim_process(tracks, img_names, T_wcs, P_cws, img_h, img_w, K, representati
     return out_dict
 
 
+def optim_process_scenes(scenes, rows, representation, prior, n_iters, n_views, fitter=None):
+    """optim_process(..., return_params=True, rows=block) for MANY scenes in the launches of one: ONE SqFitter.prepare_scenes
+    for the tracks of all scenes, the device-side packing of the constrained views, ONE SqFitter.fit for the fitted tracks of all
+    scenes, ONE compute_oriented_bboxes, and a split into one dict per scene -- each equal to the single-scene call's, key for key and
+    bit for bit.
+
+    scenes: one dict per scene: "img_names", "P_cws", "img_h", "img_w", and "tracks": the host list, None, or a callable without
+    arguments that returns it (called once, after the fit has been enqueued).  rows: the combined packed block of the scenes' tracks
+    (track_store.pack_scenes), scene s owning tracks trk_off[s] .. trk_off[s + 1] - 1.  representation ("super_quadric", "cube" or
+    "quadric"; "dual_quadric" is refused), prior, n_iters and n_views are shared.
+
+    A scene takes no part in the fit where the single-scene call would leave the device prelude: it holds no track, its frame ids are
+    not all different, or one of its tracks comes back from the prelude kernel with a status.  Such scenes are decided from the one
+    copy prepare_scenes makes anyway and REPORTED, not host-pathed here.  Returns (outs, left): outs[s] the scene's dict, or None for a
+    scene that was left out; left = {s: reason}."""
+    import torch
+    if representation == "dual_quadric":
+        raise ValueError('optim_process_scenes: representation "dual_quadric" is not fitted over scenes (super_quadric, cube and quadric are)')
+    if representation not in _sq.REPRESENTATIONS:
+        raise ValueError(f"optim_process_scenes: unknown representation {representation!r}")
+    fitter = fitter or default_fitter()
+    S = len(scenes)
+    trk = np.asarray(rows["trk_off"], np.int64)
+    offs = np.asarray(rows["row_offsets"], np.int64)
+    if len(trk) != S + 1 or int(trk[-1]) != int(rows["n_tracks"]):
+        raise ValueError(f"optim_process_scenes: the block holds {len(trk) - 1} scenes and {int(rows['n_tracks'])} tracks, {S} scenes were given")
+    later = [sc["tracks"] if callable(sc.get("tracks")) else None for sc in scenes]
+    tracks = [None if later[s] is not None else scenes[s].get("tracks") for s in range(S)]
+    for s in range(S):
+        if tracks[s] is not None and len(tracks[s]) != trk[s + 1] - trk[s]:
+            raise ValueError(f"optim_process_scenes: rows holds {int(trk[s + 1] - trk[s])} tracks of scene {s}, the list {len(tracks[s])}")
+    left = {}
+    for s, sc in enumerate(scenes):
+        if trk[s + 1] == trk[s]:
+            left[s] = "the block holds no track"
+        elif not _UniqueFrames.applies(sc["img_names"]):
+            left[s] = "the frame ids of img_names are not all different integers inside int32"
+    n_all = int(trk[-1])
+    lens = np.diff(offs)
+    scene_of = np.repeat(np.arange(S), np.diff(trk))
+    # a scene that is out already keeps its tracks in the launch with an empty image table: no view, a status, nothing to decide twice
+    prep = fitter.prepare_scenes(rows["rows14"], offs, trk, [None if s in left else sc["img_names"] for s, sc in enumerate(scenes)],
+                                 [None if s in left else sc["P_cws"] for s, sc in enumerate(scenes)], [sc["img_h"] for sc in scenes],
+                                 [sc["img_w"] for sc in scenes], representation)
+    if rows.get("check") is not None:
+        rows["check"]()
+    for s in np.unique(scene_of[prep["status"] != 0]).tolist():
+        left.setdefault(int(s), "a track came back from the prelude kernel with a status (no view, a class that is no integer in 0..63, too many rows)")
+    keep = np.array([s not in left for s in range(S)], bool)
+    in_fit = keep[scene_of] if n_all else np.zeros(0, bool)
+    classes = [int(c) for c in prep["cls"]]
+    if prior:
+        for i in np.flatnonzero(in_fit):
+            if classes[i] not in _sq.CLASS_MAPPER:
+                raise KeyError(classes[i])  # sq_libs.py:464, where the single-scene call raises it
+    fit = in_fit & (prep["n_valid"] >= n_views)
+    fit_ids = [int(i) for i in np.flatnonzero(fit)]
+    fit_counts = [int(c) for c in prep["n_valid"][fit]]
+    out = None
+    if fit_ids:      # _prelude_from_rows's packing, over the tracks of all scenes
+        dev = prep["valid"].device
+        R, K = int(offs[-1]), int(sum(fit_counts))
+        sel = (prep["valid"] != 0) & torch.from_numpy(np.repeat(fit, lens)).to(dev)
+        pos = torch.cumsum(sel, 0) - 1
+        idx = torch.empty(K + 1, device=dev, dtype=torch.int64)
+        idx.scatter_(0, torch.where(sel, pos, torch.full_like(pos, K)), torch.arange(R, device=dev))
+        idx = idx[:K]
+        p0 = prep["init"].index_select(0, torch.as_tensor(fit_ids, device=dev))
+        out = fitter.fit(p0, [classes[i] for i in fit_ids], fit_counts, prep["P"].index_select(0, idx), prep["tgt"].index_select(0, idx),
+                         prep["mask"].index_select(0, idx), n_iters=n_iters, representation=representation, prior=bool(prior), want_points=True)
+    for s in range(S):
+        if later[s] is not None and keep[s]:
+            tracks[s] = later[s]()
+    box = prep["bboxes_dl"].cpu().numpy()
+    init = prep["init"].cpu().numpy()
+    params = {i: init[i] for i in range(n_all)}
+    points, boxes = {}, {}
+    if fit_ids:
+        fp, fpts = out["params"].cpu().numpy(), out["points"].cpu().numpy()
+        for j, i in enumerate(fit_ids):
+            params[i], points[i] = fp[j], fpts[j]
+        bl, _ = compute_oriented_bboxes(fpts)
+        boxes = dict(zip(fit_ids, bl))
+    outs = []
+    for s in range(S):
+        if not keep[s]:
+            outs.append(None)
+            continue
+        ids = range(int(trk[s]), int(trk[s + 1]))
+        quadrics = [SuperQuadric(params[i], classes[i], points.get(i), fitter) for i in ids]
+        outs.append({"tracks": tracks[s], "bboxes_qc": [boxes[i] if i in points else box[i] for i in ids], "bboxes_dl": [box[i] for i in ids],
+                     "quadrics": quadrics, "params": np.stack([params[i] for i in ids]), "fitted": np.array([i in points for i in ids], bool)})
+    return outs, left
+
+
 def _host(x):
     return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
 

@@ -158,6 +158,136 @@ def map_scene(proc, tracks=None, resident_rows=False, device_merge=False, stages
     return out2
 
 
+def _shared_settings(procs):
+    """what the process objects of map_scenes must have in common, read without touching the device: (fit settings, fitter key)"""
+    first = None
+    for i, p in enumerate(procs):
+        fit = p.fit_settings() if hasattr(p, "fit_settings") else None
+        if fit is None:
+            raise ValueError(f"map_scenes: process {i} does not say how it fits (OdamProcess.fit_settings)")
+        if fit["representation"] == "dual_quadric":
+            raise ValueError(f'map_scenes: process {i} fits "dual_quadric", which is not fitted over scenes (map_scene takes it)')
+        dev = str(getattr(getattr(p, "detector", None), "device", "cuda:0"))
+        f = p.fitter if p.fitter is not None else multi_view._DEFAULT_FITTER.get(dev, ("default fitter", dev))
+        if first is None:
+            first = (fit, f)
+        elif fit != first[0]:
+            raise ValueError(f"map_scenes: process {i} fits with {fit}, process 0 with {first[0]}: representation, prior, steps and n_views are shared")
+        elif f is not first[1] and f != first[1]:
+            raise ValueError(f"map_scenes: process {i} has another fitter (or device) than process 0: one launch runs on one SqFitter")
+    return first
+
+
+def map_scenes(procs, loaded=False, stages=None):
+    """map_scene(proc, resident_rows=True, loaded=loaded) for every process object of the list, in the launches of ONE scene:
+    the rows of all stores as one block (track_store.pack_scenes), pass 1 as one multi_view.optim_process_scenes, the merge as one
+    merge.merge_packed_scenes, the stores' adoption of the merged rows with one copy back (track_store.adopt_scenes), pass 2 as one
+    optim_process_scenes.  Returns the list of second-pass dicts, each the bits of the single-scene call.
+
+    All procs share one fitter (hence device), representation, prior setting, step count and n_views -- ValueError before any device
+    work otherwise, and for "dual_quadric".  A scene leaves the batch only for a reason map_scene itself has: its store refuses the
+    list, a prelude status, a scene merge._device_scene refuses, a merge status -- decided from the copies the batch makes anyway.  One
+    that leaves before or at the first prelude goes through map_scene; one that leaves at the merge (or at the second prelude) completes
+    its second pass in map_scene's own code path; both after the batch.
+    stages: fit1, merge, fit2 (seconds of the batch), first_pass (list of dicts), batched (indices that went through all three steps in
+    the batch), single (the others)."""
+    import time
+    from . import merge, track_store
+    procs = list(procs)
+    n = len(procs)
+    if n == 0:
+        if stages is not None:
+            stages.update(fit1=0.0, merge=0.0, fit2=0.0, first_pass=[], batched=[], single=[])
+        return []
+    fit, _ = _shared_settings(procs)
+    if loaded:
+        for i, p in enumerate(procs):
+            if getattr(p, "_rows", None) is None:
+                raise ValueError(f"map_scenes(loaded=True): process {i} has no row store that was fed (track_frames_packed(resident=True))")
+    fitter = procs[0]._fitter()
+    release = [getattr(p, "_release_store", lambda: None) for p in procs]
+    stores, tracks, alone = [None] * n, [None] * n, []
+    for i, p in enumerate(procs):
+        if loaded:
+            stores[i], tracks[i] = p._rows, p._rows.host_tracks
+            continue
+        release[i]()
+        if p._rows is None:
+            p._rows = track_store.TrackRows(fitter)
+        tracks[i] = p.tracks
+        if p._rows.load(tracks[i]) is None:
+            alone.append(i)      # map_scene's host path
+        else:
+            stores[i] = p._rows
+    first, second = [None] * n, [None] * n
+    meta = lambda p: {"img_names": p.usable_frames, "P_cws": p.P_cws, "img_h": p.sequence_meta.img_h, "img_w": p.sequence_meta.img_w}
+    args = (fit["representation"], fit["prior"], fit["n_iters"], fit["n_views"])
+
+    s0 = time.perf_counter()
+    ids = [i for i in range(n) if stores[i] is not None]
+    if ids:
+        outs, left = multi_view.optim_process_scenes([dict(meta(procs[i]), tracks=tracks[i]) for i in ids],
+                                                     track_store.pack_scenes([stores[i] for i in ids]), *args, fitter=fitter)
+        for k, i in enumerate(ids):
+            if k in left:
+                alone.append(i)
+            else:
+                first[i] = outs[k]
+                release[i]()      # (loaded: the list was downloaded under the fit; the store is about to hold other rows)
+                procs[i]._refine_state = None
+        ids = [i for k, i in enumerate(ids) if k not in left]
+    s1 = time.perf_counter()
+
+    finish = {}      # scenes that complete their second pass as map_scene does: index -> callable
+    block = None
+    if ids:
+        block, per = merge.merge_packed_scenes([first[i] for i in ids], [procs[i].usable_frames for i in ids], fitter=fitter,
+                                               rows=track_store.pack_scenes([stores[i] for i in ids]))
+        went = [i for k, i in enumerate(ids) if per[k] is not None]
+        for k, i in enumerate(ids):
+            if per[k] is None:
+                finish[i] = lambda i=i: _second_pass_alone(procs[i], stores[i], first[i])
+        if went:
+            track_store.adopt_scenes([stores[i] if per[k] is not None else None for k, i in enumerate(ids)], block)
+        order, ids = ids, went
+    s2 = time.perf_counter()
+
+    if ids:
+        host = {}
+
+        def merged_tracks(i):      # the merged host tracks of all scenes: ONE copy back, made under pass 2
+            if not host:
+                host.update(zip(order, merge.tracks_from_packed_scenes(block, [first[j] for j in order])))
+            return host[i]
+        outs, left = multi_view.optim_process_scenes([dict(meta(procs[i]), tracks=lambda i=i: merged_tracks(i)) for i in ids],
+                                                     track_store.pack_scenes([stores[i] for i in ids]), *args, fitter=fitter)
+        for k, i in enumerate(ids):
+            if k in left:      # optim_process(rows=...) falls back on the host list there
+                finish[i] = lambda i=i: procs[i].optim_process(lambda: merged_tracks(i), return_params=True, rows=stores[i].packed())
+            else:
+                second[i] = outs[k]
+        ids = [i for k, i in enumerate(ids) if k not in left]
+    s3 = time.perf_counter()
+
+    for i, f in finish.items():
+        second[i] = f()
+    for i in alone:
+        st = {}
+        second[i] = map_scene(procs[i], None if loaded else tracks[i], resident_rows=True, stages=st, loaded=loaded)
+        first[i] = st["first_pass"]
+    if stages is not None:
+        stages.update(fit1=s1 - s0, merge=s2 - s1, fit2=s3 - s2, first_pass=first, batched=sorted(ids),
+                      single=sorted(set(range(n)) - set(ids)))
+    return second
+
+
+def _second_pass_alone(proc, store, out):
+    """map_scene's own lines for a scene the device merge does not take: the host merge, a load of the merged tracks, pass 2"""
+    merged = proc.merge_process(out)
+    block2 = store.packed() if store.load(merged) is not None else None
+    return proc.optim_process(merged, return_params=True, rows=block2) if block2 is not None else proc.optim_process_params(merged)
+
+
 def run_scene(proc, n_frames, frame_ids, T_wcs, detect=None, frames=None, chunk=0, device=None, force=False, stages=None, overlap=None,
               device_select=False, device_merge=False):
     """The driver loop of run_processor.py:70-83 for one scene on the ranks of the current process group.

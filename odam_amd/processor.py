@@ -896,15 +896,21 @@ class OdamProcess:
             return {"prelude": "device"}
         return {"prelude": "device", "rows": self._rows.packed()}
 
+    def fit_settings(self):
+        """what optim_process hands multi_view.optim_process besides the sequence: the settings processes must share to be fitted in
+        one call (pipeline.map_scenes)"""
+        # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
+        return {"representation": self.representation, "prior": True, "n_iters": 500 if self.representation == "dual_quadric" else 200,
+                "n_views": 10}
+
     def optim_process(self, tracks, return_params=False, prelude=None, rows=None):
         """prelude: "host", "device" (multi_view.optim_process), "resident" (the device prelude on the row store, self._rows), or None for
         what self.resident_rows / self.device_prelude say.  rows: a packed block that stands for the tracks' rows (multi_view.optim_process;
         pipeline.map_scene passes its store's), whatever prelude says"""
         m = self.sequence_meta
-        # (QuadricOptimizer.run takes 500 steps whatever it is told, sq_libs.py:227)
-        n_iters = 500 if self.representation == "dual_quadric" else 200
+        fit = self.fit_settings()
         return multi_view.optim_process(tracks, self.usable_frames, self.T_wcs, self.P_cws, m.img_h, m.img_w, m.K,
-                                        self.representation, prior=True, n_iters=n_iters, n_views=10,
+                                        fit["representation"], prior=fit["prior"], n_iters=fit["n_iters"], n_views=fit["n_views"],
                                         fitter=self._fitter(), return_params=return_params,
                                         **({"rows": rows} if rows is not None else self._prelude_args(prelude, tracks, self._fitter())))
 

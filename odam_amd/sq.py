@@ -120,6 +120,17 @@ def _prepare_entry():
     return f
 
 
+# odam_sq_prepare_scenes as include/odam_sq.h declares it (tests/test_map_scenes_host.py holds the two together)
+PREPARE_SCENES_ARGTYPES = [_VP, _CI, _VP, _VP, _CI, _CI, _VP, _VP, _CI, _VP, _VP, _VP, _VP, _VP, _CD, _CI] + [_VP] * 15
+
+
+def _prepare_scenes_entry():
+    f = _lib.lib().odam_sq_prepare_scenes
+    if f.argtypes is None:
+        f.argtypes, f.restype = PREPARE_SCENES_ARGTYPES, ctypes.c_int
+    return f
+
+
 # odam_merge_cluster / odam_merge_assemble as include/odam_merge.h declares them (tests/test_track_merge_host.py holds them together)
 _LL = ctypes.c_longlong
 MERGE_ARGTYPES = {
@@ -411,6 +422,119 @@ class SqFitter:
                     float(img_w), float(img_h), float(thr), rep, _lib.ptr(ints[0]), _lib.ptr(ints[1]), _lib.ptr(ints[2]), _lib.ptr(init),
                     _lib.ptr(half), _lib.ptr(pose), _lib.ptr(box), _lib.ptr(ints[3]), _lib.ptr(view_img), _lib.ptr(view_row), _lib.ptr(tgt),
                     _lib.ptr(mask), _lib.ptr(P), _lib.ptr(valid), ctypes.c_void_p(stream)), "odam_sq_prepare_batch")
+            h = ints[:, :n].cpu().numpy()
+        else:      # no row at all: every track is one without a view
+            h = np.zeros((4, n), np.int32)
+            h[0], h[3] = -1, PREPARE_NO_VIEW
+        return {"cls": h[0], "n_obs": h[1], "n_valid": h[2], "status": h[3], "init": init, "half_dims": half, "pose": pose, "bboxes_dl": box,
+                "view_img": view_img[:R], "view_row": view_row[:R], "valid": valid[:R], "tgt": tgt[:R], "mask": mask[:R], "P": P[:R],
+                "row_offsets": d_off}
+
+    def prepare_scenes(self, rows, row_offsets, trk_off, img_names_list, P_cws_list, img_hs, img_ws, representation="super_quadric",
+                       thr=EDGE_THRESHOLD, max_rows=None):
+        """prepare for the tracks of MANY scenes in one launch (include/odam_sq.h, odam_sq_prepare_scenes): every output word is the
+        word prepare returns for that scene alone.
+
+        rows, row_offsets, max_rows as prepare takes them, the tracks of all scenes one after the other; trk_off [n_scene + 1] on the
+        host: scene s owns tracks trk_off[s] .. trk_off[s + 1] - 1 (an empty scene is legal); img_names_list, P_cws_list, img_hs,
+        img_ws: per scene what prepare takes per call -- the image tables are built with frame_tables per scene, as merge_assemble
+        builds them, so the same frame id may appear in several scenes.  max_rows may also be one value per scene.  Returns prepare's
+        dict ("view_img" is the image index inside the track's scene) with ONE small copy back: cls, n_obs, n_valid, status.
+
+        prepare sizes its launch from the longest track it is given, and the size decides the order of the sums behind a track's yaw;
+        so that a scene's words do not depend on what else is in the call, the kernel is told every scene's own size (scene_rows of
+        the header): from host offsets the longest track of each scene, as prepare would find it; with a max_rows per scene, those;
+        with device offsets and one max_rows (or none), that value for every scene, as prepare(max_rows=...) would take it."""
+        dev = self.device
+        rep = REPRESENTATIONS[representation]
+        to = np.asarray(trk_off.cpu().numpy() if torch.is_tensor(trk_off) else trk_off).astype(np.int64).reshape(-1)
+        if len(to) < 1 or to[0] != 0 or (np.diff(to) < 0).any():
+            raise ValueError("prepare_scenes: trk_off must start at 0 and not decrease")
+        n_scene = len(to) - 1
+        if not (len(img_names_list) == len(P_cws_list) == len(img_hs) == len(img_ws) == n_scene):
+            raise ValueError(f"prepare_scenes: image names, projections, heights and widths must be given once for each of the {n_scene} scenes")
+        if torch.is_tensor(row_offsets) and row_offsets.is_cuda:
+            d_off = row_offsets.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+            offs = None
+            n = d_off.shape[0] - 1
+            if max_rows is None:
+                max_rows = PREPARE_MAX_ROWS
+        else:
+            offs = np.asarray(row_offsets.numpy() if torch.is_tensor(row_offsets) else row_offsets).astype(np.int64).reshape(-1)
+            if len(offs) < 1 or offs[0] != 0 or (np.diff(offs) < 0).any() or offs[-1] != len(rows) or offs[-1] >= 2 ** 31:
+                raise ValueError(f"prepare_scenes: row_offsets must run from 0 to the {len(rows)} rows given without decreasing")
+            d_off = None
+            n = len(offs) - 1
+        if int(to[-1]) != n:
+            raise ValueError(f"prepare_scenes: trk_off ends at {int(to[-1])}, row_offsets holds {n} tracks")
+        if max_rows is None:      # host offsets: every scene as prepare would size it
+            lens = np.diff(offs)
+            scene_rows = np.array([max(int(lens[to[s]:to[s + 1]].max()), 1) if to[s + 1] > to[s] else 1 for s in range(n_scene)], np.int64)
+        else:
+            scene_rows = np.broadcast_to(np.asarray(max_rows, np.int64), (n_scene,)).copy()
+            scene_rows = np.clip(scene_rows, 1, PREPARE_MAX_ROWS)
+        max_rows = int(scene_rows.max()) if n_scene else 1
+        d_rows = self._as_dev(rows, torch.float64)
+        if d_rows.dim() != 2 or d_rows.shape[1] != 14:
+            raise ValueError(f"prepare_scenes: rows must be [R, 14], got {tuple(d_rows.shape)}")
+        R = d_rows.shape[0]
+        # (img_names_list[s] = None: a scene without an image -- every track of it comes back without a view, status 1)
+        tables = [(np.zeros(0, np.int64), np.zeros(0, np.int32)) if names is None else frame_tables(names) for names in img_names_list]
+        io = np.zeros(n_scene + 1, np.int64)
+        io[1:] = np.cumsum([len(t[0]) for t in tables])
+        n_img = int(io[-1])
+        ids = np.concatenate([t[0] for t in tables] + [np.zeros(1, np.int64)])      # (one spare word: never a null pointer)
+        order = np.concatenate([t[1] for t in tables] + [np.zeros(1, np.int32)])
+        wh = np.zeros((n_scene, 2), np.float64)
+        wh[:, 0], wh[:, 1] = [float(w) for w in img_ws], [float(h) for h in img_hs]
+        # the small tables travel in TWO uploads, whatever the number of scenes: the 32-bit words (offsets, scene sizes, image order) and
+        # the 64-bit words (image sizes, frame ids as their bits, and the projections where they are host arrays)
+        words = [np.asarray(a, np.int64).astype(np.int32) for a in ((offs,) if offs is not None else ()) + (to, io, scene_rows)] + [order]
+        d32 = torch.from_numpy(np.concatenate(words)).to(dev)
+        cuts = np.cumsum([0] + [len(a) for a in words])
+        parts = [d32[cuts[i]:cuts[i + 1]] for i in range(len(words))]
+        if offs is not None:
+            d_off, parts = parts[0], parts[1:]
+        d_toff, d_ioff, d_srows, d_ord = parts
+        host_P = not any(torch.is_tensor(P) for P in P_cws_list)
+        Ps = [None if names is None else (np.asarray(P, np.float64).reshape(-1, 12) if host_P else self._as_dev(P, torch.float64).reshape(-1, 12))
+              for P, names in zip(P_cws_list, img_names_list)]
+        for s, (P, t) in enumerate(zip(Ps, tables)):
+            if P is not None and P.shape[0] != len(t[0]):
+                raise ValueError(f"prepare_scenes: scene {s} has {P.shape[0]} projections for {len(t[0])} images")
+        Ps = [P for P in Ps if P is not None and P.shape[0]]
+        quads = [wh.reshape(-1), ids.view(np.float64)] + ([P.reshape(-1) for P in Ps] if host_P else [])
+        d64 = torch.from_numpy(np.concatenate(quads)).to(dev)
+        d_wh, d_ids = d64[:2 * n_scene], d64[2 * n_scene:2 * n_scene + len(ids)].view(torch.int64)
+        if not n_img:
+            d_Pc = torch.zeros(1, 12, device=dev, dtype=torch.float64)      # (never a null pointer)
+        elif host_P:
+            d_Pc = d64[2 * n_scene + len(ids):].reshape(-1, 12)
+        else:
+            d_Pc = torch.cat(Ps)
+        if not n_scene:
+            d_wh = torch.zeros(2, device=dev, dtype=torch.float64)
+        ints = torch.empty(4, max(n, 1), device=dev, dtype=torch.int32)      # cls, n_obs, n_valid, status: read back in one copy
+        init = torch.empty(n, 5 if rep == 3 else 9, device=dev, dtype=torch.float32)
+        half = torch.empty(n, 3, device=dev, dtype=torch.float32) if rep == 3 else None
+        pose = torch.empty(n, 7, device=dev, dtype=torch.float64)
+        box = torch.empty(n, 8, 3, device=dev, dtype=torch.float64)
+        pad = max(R, 1)      # (an empty tensor has no pointer to pass)
+        view_img = torch.empty(pad, device=dev, dtype=torch.int32)
+        view_row = torch.empty(pad, device=dev, dtype=torch.int32)
+        valid = torch.zeros(pad, device=dev, dtype=torch.int32)      # 0 wherever the kernel writes no view: a mask over all R rows
+        tgt = torch.empty(pad, 4, device=dev, dtype=torch.float32)
+        mask = torch.empty(pad, 4, device=dev, dtype=torch.float32)
+        P = torch.empty(pad, 12, device=dev, dtype=torch.float32)
+        if n and R:
+            with torch.cuda.device(dev), self._lock:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_prepare_scenes_entry()(
+                    self._h, n, _lib.ptr(d_off), _lib.ptr(d_rows), max(int(max_rows), 1), n_scene, _lib.ptr(d_toff), _lib.ptr(d_ioff), n_img,
+                    _lib.ptr(d_ids), _lib.ptr(d_ord), _lib.ptr(d_Pc), _lib.ptr(d_wh), _lib.ptr(d_srows), float(thr), rep, _lib.ptr(ints[0]), _lib.ptr(ints[1]),
+                    _lib.ptr(ints[2]), _lib.ptr(init), _lib.ptr(half), _lib.ptr(pose), _lib.ptr(box), _lib.ptr(ints[3]), _lib.ptr(view_img),
+                    _lib.ptr(view_row), _lib.ptr(tgt), _lib.ptr(mask), _lib.ptr(P), _lib.ptr(valid), ctypes.c_void_p(stream)),
+                    "odam_sq_prepare_scenes")
             h = ints[:, :n].cpu().numpy()
         else:      # no row at all: every track is one without a view
             h = np.zeros((4, n), np.int32)

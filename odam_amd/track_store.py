@@ -243,6 +243,24 @@ class TrackRows:
         lens_d = (off_d[1:] - off_d[:-1])
         self._tid = torch.repeat_interleave(torch.arange(T, device=rows.device, dtype=torch.int32), lens_d, output_size=self.n_rows)
 
+    def _take(self, rows, lengths, marks, lens_d=None):
+        """the end of adopt_scenes for one store: `rows` [n_rows, 14] on the device, track after track, is the log from now on; lengths
+        and marks are the host's -- the state adopt leaves"""
+        self.reset()
+        self.lengths = [int(k) for k in lengths]
+        self.marks = np.ascontiguousarray(marks, np.float64).reshape(len(self.lengths), 3)
+        self.n_rows = int(sum(self.lengths))
+        self.capacity = max(self.n_rows, 1)
+        self._set_log(rows, lens_d)
+
+    def _set_log(self, rows, lens_d=None):
+        """(device side of _take; lens_d: the lengths where they lie on the device already, so that nothing is uploaded)"""
+        import torch
+        self._log = rows[:self.n_rows].contiguous()
+        if lens_d is None:
+            lens_d = torch.as_tensor(self.lengths, dtype=torch.int64).to(rows.device)
+        self._tid = torch.repeat_interleave(torch.arange(len(self.lengths), device=rows.device, dtype=torch.int32), lens_d, output_size=self.n_rows)
+
     # ---- rows that are born on the device (include/odam_rows.h: odam_rows_emit_tracked, odam_rows_marks) -----------------------------------
     def _emit(self, blk, cnt, ids, T_wcs, cam_azi, img_w, img_h, n_tracks, base):
         """the device side of append_tracked (a test's stub overrides it): both launches on the current stream, then the ONE copy back,
@@ -366,3 +384,70 @@ class TrackRows:
                                          "(1: a track id outside the list, 2: a track whose row count is not the host's)")
         self._block = {"rows14": rows14, "row_offsets": off, "max_rows": int(max(self.lengths)) if T else 0, "n_tracks": T, "check": check}
         return self._block
+
+
+# ---- many scenes in one block (pipeline.map_scenes) ---------------------------------------------------------------------------
+
+def _concat_rows(pieces):
+    """the rows of several blocks one after the other, device to device (a test's stub overrides it)"""
+    import torch
+    return pieces[0] if len(pieces) == 1 else torch.cat(pieces)
+
+
+def _adopt_copy(rows, off_d):
+    """adopt_scenes' ONE copy back (a test's stub overrides it): off_d [T + 1] on the device -> float64 numpy [T + 1 + 3 T]: the offsets, then
+    the frame id of every track's first row, the frame id of its last row, the world x of its last row"""
+    import torch
+    off_d = off_d.to(torch.int64)
+    first, last = rows.index_select(0, off_d[:-1]), rows.index_select(0, off_d[1:] - 1)
+    return torch.cat([off_d.to(torch.float64), first[:, 0], last[:, 0], last[:, 9]]).cpu().numpy()
+
+
+def pack_scenes(stores):
+    """The packed blocks of S stores as ONE block, scene after scene: {"rows14", "row_offsets", "trk_off", "max_rows", "n_tracks", "check"}
+    -- what packed() returns, plus "trk_off" [S + 1] int64: scene s owns tracks trk_off[s] .. trk_off[s + 1] - 1 (an empty store is an
+    empty scene).  The rows are concatenated on the device; nothing is uploaded or read back.  check() calls every block's own."""
+    blocks = [st.packed() for st in stores]
+    trk_off = np.zeros(len(blocks) + 1, np.int64)
+    trk_off[1:] = np.cumsum([b["n_tracks"] for b in blocks])
+    offs, base = [np.zeros(1, np.int64)], 0
+    for b in blocks:
+        o = np.asarray(b["row_offsets"], np.int64)
+        offs.append(o[1:] + base)
+        base += int(o[-1])
+    pieces = [b["rows14"] for b in blocks if int(b["row_offsets"][-1])]
+    rows14 = _concat_rows(pieces) if pieces else (blocks[0]["rows14"] if blocks else None)
+    checks = [b["check"] for b in blocks]
+
+    def check():
+        for c in checks:
+            c()
+    return {"rows14": rows14, "row_offsets": np.concatenate(offs), "trk_off": trk_off, "max_rows": max([b["max_rows"] for b in blocks], default=0),
+            "n_tracks": int(trk_off[-1]), "check": check}
+
+
+def adopt_scenes(stores, merged):
+    """TrackRows.adopt for S stores from ONE merged block (merge.merge_packed_scenes): "rows14" and "row_offsets" on the device for the
+    merged tracks of all scenes one after the other, "n_out" [S] on the host: merged tracks per scene.  Every store gets what adopt
+    would have given it from its own scene's block -- lengths, marks, n_rows, and a log that holds the same bits -- with ONE copy back
+    for all scenes (the offsets and the marks).  stores[s] = None leaves scene s alone (its rows are in the block all the same)."""
+    n_out = [int(k) for k in merged["n_out"]]
+    if len(n_out) != len(stores):
+        raise ValueError(f"adopt_scenes: {len(stores)} stores for the {len(n_out)} scenes of the block")
+    T = int(sum(n_out))
+    rows = merged["rows14"]
+    if T > 0 and rows.shape[0]:
+        small = _adopt_copy(rows, merged["row_offsets"][:T + 1])
+        off = small[:T + 1].astype(np.int64)
+        marks = np.ascontiguousarray(small[T + 1:].reshape(3, T).T)
+    else:
+        off, marks = np.zeros(T + 1, np.int64), np.zeros((T, 3))
+    lens_d = None
+    if T > 0:
+        off_d = merged["row_offsets"][:T + 1].to(merged["rows14"].device).long()
+        lens_d = off_d[1:] - off_d[:-1]
+    o = 0
+    for st, k in zip(stores, n_out):
+        if st is not None:
+            st._take(rows[int(off[o]):int(off[o + k])], np.diff(off[o:o + k + 1]), marks[o:o + k], None if lens_d is None else lens_d[o:o + k])
+        o += k
